@@ -3,14 +3,18 @@
 backward + clip + AdamW) on synthetic all-MiniLM-L6-v2-shaped batches, seq_len=128, 64 quadruplets
 per GPU (BASELINE.json configs[1]; configs[3] when launched with N > 1 ranks).
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line (contract in the task statement): value = whole-job quadruplets/s with the
-inputs resident in HBM; `roofline` = the dominant kernel's achieved TFLOP/s (its algorithmic FLOPs per
-launch / its average launch duration measured here with HIP events) against the dense bf16 MFMA peak;
-`cpu_baseline` = the CPU oracle (oracle/torch_ref.py) timed on this box's host cores, rank 0, N=1 only.
+inputs resident in HBM, ms_per_step = wall time of one timed step. A plain run sets up, warms up, times the
+steps, writes the last timed step's outputs with --dump-outputs and prints the line. --full adds the side
+measurements, each of which runs work of its own: `step_without_dropout`; `roofline` = the dominant kernel's
+achieved TFLOP/s (its algorithmic FLOPs per launch / its average launch duration measured here with HIP events)
+against the dense bf16 MFMA peak; the forward-only and other-precision figures, golden parity and the RCCL path
+(unless --no-extras); `cpu_baseline` = the CPU oracle (oracle/torch_ref.py) timed on this box's host cores, rank 0,
+N=1 only (unless --no-cpu-baseline).
 """
 import argparse
 import json
@@ -54,6 +58,12 @@ def parse():
                          "trace belongs to the headline step (or is one of the --kernel-reps direct launches)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the forward-only and loss-kernel side measurements (profiled runs: keeps per-step kernel counts clean)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: the step without dropout, the roofline kernel timings (--kernel-reps), "
+                         "the extras (--no-extras) and the CPU baseline (--no-cpu-baseline); off: the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, gradient norm, a fixed sample of the "
+                         "updated parameters) as DIR/<name>.npy, float32")
     return ap.parse_args()
 
 
@@ -618,6 +628,32 @@ def time_dp_rccl_ws1(trainer, cfg, batches, steps, B, ms_dp1):
         return {"error": f"{type(e).__name__}: {e}"[:300]}
 
 
+DUMP_SAMPLE = 1 << 21         # parameter positions kept by --dump-outputs (8 MB in fp32)
+
+
+def dump_outputs(trainer, loss, out_dir):
+    """What the timed path hands its caller after its last step, as float32 .npy files in out_dir: the loss, the gradient
+    norm the clip measured (before clipping) and the parameters the step left behind. Arenas larger than DUMP_SAMPLE are
+    sampled at DUMP_SAMPLE distinct positions drawn from a fixed seed: the same positions in every run of the same model.
+    The AdamW moments stay out: they are the optimizer's own state, and over a few dozen dropout steps the fp32 atomics'
+    summation order flips hinge terms of the loss, which moves single moments by several percent from run to run, while
+    the loss, the norm and the parameters repeat to ~1e-5 relative or better."""
+    import numpy as np
+    import torch
+    e = trainer.enc
+    torch.cuda.synchronize()
+    n = e.params.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(14).choice(n, DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(pos).to(e.params.device)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.reshape(-1), "grad_norm": e.grad_norm.reshape(-1),
+              "params": e.params if idx is None else e.params[idx]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     args = parse()
     # The contract is ONE line on stdout. Libraries write there too (RCCL prints a five-line version banner when its first
@@ -707,9 +743,12 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
     final_loss = float(loss.item())
+    # before any side figure trains on: the outputs of the last timed step (the replicas are identical, rank 0 writes them)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, loss, args.dump_outputs)
     # side figure: the same step with dropout off (what rounds 1 measured; eager path only -- a captured graph holds its masks' launches)
     no_drop = None
-    if args.dropout > 0 and not args.graph and not args.profile:
+    if args.full and args.dropout > 0 and not args.graph and not args.profile:
         trainer.enc.set_dropout(0.0, 0.0)
         for i in range(3):
             trainer.step(*batches[i % nb])
@@ -729,11 +768,36 @@ def main():
 
     out = None
     # every rank runs the kernel timing: its interleaved training steps are collective (gradient all-reduce)
-    dk, dk2, dk3 = time_kernels(trainer, 4 * B, L, args.kernel_reps, batches)
+    if args.full:
+        dk, dk2, dk3 = time_kernels(trainer, 4 * B, L, args.kernel_reps, batches)
     if rank == 0:
         fwd_flops_q = 4.0 * forward_flops_per_sequence(cfg, L)
         train_flops_q = 3.0 * fwd_flops_q
         step_tflops = value * train_flops_q / 1e12
+        out = {
+            "metric": f"quadruplets/sec (seq_len={L}, {args.model}) training step", "value": round(value, 1),
+            "unit": "quadruplets/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "ms_per_step_median": round(ms_median, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": {"bf16": "bf16", "f16": "f16", "f16w": "f16 (split-f16 weights in the forward)", "fp8": "fp8 (MXFP8 forward GEMMs, bf16 backward)", "bf16x3": "bf16x3 (fp32-class)"}[args.train_precision],
+            "data": "synthetic",
+            "config": {"workload": f"{args.model} dims (random-init), {B} quadruplets/GPU x {world} GPU, seq_len={L}, "
+                                   "fwd + gamma-quadruplet loss + bwd + clip + AdamW, "
+                                   + (f"dropout {args.dropout:g} on hidden states and attention probabilities as the reference's "
+                                      "train() mode" if args.dropout > 0 else "dropout off") + f" ({baseline_config_name(args.model, B, L, world, args.train_precision)})",
+                       "global_batch": B * world, "seq_len": L,
+                       "parallelism": f"dp{world}" + (" through RCCL (world_size 1: staged backward + 7 async all-reduces)" if args.force_dp else ""),
+                       "precision": {"bf16": "bf16 MFMA operands, fp32 accumulate/residual/LN/softmax/loss/optimizer",
+                                     "f16": "IEEE-half MFMA operands under a device-side dynamic loss scale, fp32 accumulate/residual/LN/softmax/loss/optimizer",
+                                     "f16w": "as f16, every forward Linear against hi + lo of its weight (two f16 values per weight)",
+                                     "fp8": "forward Linears on the fp8 matrix cores (MXFP8 weights and activations), bf16 attention "
+                                            "and backward, fp32 accumulate/residual/LN/softmax/loss/optimizer",
+                                     "bf16x3": "split-bf16 x3 MFMA products on fp32 operands (fp32-class), fp32 everywhere else"}[args.train_precision],
+                       "launch": "hip graph replay" if use_graph else "eager"},
+            "loss": round(final_loss, 6),
+            "step_tflops": round(step_tflops, 2),
+            "step_mfma_frac": round(step_tflops / (PEAK_BF16_TFLOPS * world), 4),
+        }
+    if rank == 0 and args.full:
         achieved = dk["flops_per_launch"] / (dk["ms"] * 1e-3) / 1e12
         achieved2 = dk2["flops_per_launch"] / (dk2["ms"] * 1e-3) / 1e12
         # HBM bytes per launch come from a separate rocprofv3 --pmc run (they cannot be collected inside a timed run);
@@ -757,29 +821,8 @@ def main():
                     traffic_src = "stale: " + prof_name + " was measured on a different gemm.hip"
             except Exception:
                 traffic = traffic2 = None
-        out = {
-            "metric": f"quadruplets/sec (seq_len={L}, {args.model}) training step", "value": round(value, 1),
-            "unit": "quadruplets/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "ms_per_step_median": round(ms_median, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"bf16": "bf16", "f16": "f16", "f16w": "f16 (split-f16 weights in the forward)", "fp8": "fp8 (MXFP8 forward GEMMs, bf16 backward)", "bf16x3": "bf16x3 (fp32-class)"}[args.train_precision],
-            "data": "synthetic",
-            "config": {"workload": f"{args.model} dims (random-init), {B} quadruplets/GPU x {world} GPU, seq_len={L}, "
-                                   "fwd + gamma-quadruplet loss + bwd + clip + AdamW, "
-                                   + (f"dropout {args.dropout:g} on hidden states and attention probabilities as the reference's "
-                                      "train() mode" if args.dropout > 0 else "dropout off") + f" ({baseline_config_name(args.model, B, L, world, args.train_precision)})",
-                       "global_batch": B * world, "seq_len": L,
-                       "parallelism": f"dp{world}" + (" through RCCL (world_size 1: staged backward + 7 async all-reduces)" if args.force_dp else ""),
-                       "precision": {"bf16": "bf16 MFMA operands, fp32 accumulate/residual/LN/softmax/loss/optimizer",
-                                     "f16": "IEEE-half MFMA operands under a device-side dynamic loss scale, fp32 accumulate/residual/LN/softmax/loss/optimizer",
-                                     "f16w": "as f16, every forward Linear against hi + lo of its weight (two f16 values per weight)",
-                                     "fp8": "forward Linears on the fp8 matrix cores (MXFP8 weights and activations), bf16 attention "
-                                            "and backward, fp32 accumulate/residual/LN/softmax/loss/optimizer",
-                                     "bf16x3": "split-bf16 x3 MFMA products on fp32 operands (fp32-class), fp32 everywhere else"}[args.train_precision],
-                       "launch": "hip graph replay" if use_graph else "eager"},
-            "loss": round(final_loss, 6),
+        out.update({
             "step_without_dropout": no_drop,
-            "step_tflops": round(step_tflops, 2),
-            "step_mfma_frac": round(step_tflops / (PEAK_BF16_TFLOPS * world), 4),
             "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": dk["kernel"], "avg_launch_ms": round(dk["ms"], 5), "shape_M_H_I": dk["shape"],
@@ -788,7 +831,7 @@ def main():
                                   "unit": "TFLOP/s", "frac": round(achieved2 / PEAK_BF16_TFLOPS, 4), "traffic": traffic2,
                                   "kernel": dk2["kernel"], "avg_launch_ms": round(dk2["ms"], 5), "shape_MNK": dk2["shape"],
                                   "hbm_side": hbm_side(dk2)},
-        }
+        })
         if dk3 is not None:
             a3 = dk3["flops_per_launch"] / (dk3["ms"] * 1e-3) / 1e12
             out["roofline_ffn_inference"] = {"bound": "mfma", "achieved": round(a3, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
@@ -845,6 +888,7 @@ def main():
             c1arena = arena if args.model == "all-MiniLM-L6-v2" else synthetic_params(c1cfg, seed=14)
             out["cpu_baseline"], cpu_losses = cpu_baseline(c1cfg, c1arena, L, B)
             out["config1_hip"] = config1_on_gpu(c1cfg, c1arena, cpu_losses)
+    if rank == 0:
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if world > 1:

@@ -28,7 +28,7 @@ def main(src, dst):
     M, H, I = 32768, 384, 1536
     nparam = H * I + I * H + H * H + 3 * H * H
     out = {
-        "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 3 --warmup 2 "
+        "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 3 --warmup 2 "
                   "--kernel-reps 1 --no-cpu-baseline --no-extras` (in-step launches, MiniLM c2); gfx950 correction: FETCH_SIZE "
                   "counts 64 B per 128-B request for 16-B/lane streaming reads -> doubled (MI355X_MICROARCH.md, HBM); "
                   "WRITE_SIZE exact (also for float atomics); averaged per dispatch by tools/pmc_summary.py",

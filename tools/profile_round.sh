@@ -10,10 +10,10 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o w -- python3 $ROOT/bench.py --steps 20 --warmup 5 --kernel-reps 1 --no-cpu-baseline --no-extras --profile > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o w -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --kernel-reps 1 --no-cpu-baseline --no-extras --profile > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 for C in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES"; do
   D=$OUT/pmc_$(echo $C | cut -d' ' -f1)
-  rocprofv3 --pmc $C --output-format csv -d $D -o w -- python3 $ROOT/bench.py --steps 3 --warmup 2 --kernel-reps 1 --no-cpu-baseline --no-extras --profile > /dev/null 2> $D.err || true
+  rocprofv3 --pmc $C --output-format csv -d $D -o w -- python3 $ROOT/bench.py --full --steps 3 --warmup 2 --kernel-reps 1 --no-cpu-baseline --no-extras --profile > /dev/null 2> $D.err || true
 done
 cd $ROOT
 python profiles/summarize.py $(find $OUT/trace -name "*kernel_stats.csv" | head -1) 25 > $OUT/kernel_summary.txt
