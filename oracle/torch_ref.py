@@ -312,7 +312,7 @@ def _mx(x: torch.Tensor, via_bf16: bool) -> torch.Tensor:
 
 
 class _LinearMxFwdBf16Bwd(torch.autograd.Function):
-    """One Linear of the fp8 TRAINING path (csrc/qst_api.hip forward_mx_train + the bf16 backward): the forward product is
+    """One Linear of the fp8 TRAINING path (csrc/qst_api.hip Pass::forward_fp8, training, + the bf16 backward): the forward product is
     taken on MXFP8 operands, the backward is the bf16 path's -- dX = bf16(dY) . bf16(W), dW = bf16(dY)^T . bf16(X), db = column
     sums of the bf16-rounded dY -- on the UNquantised operands (fp32 master weights; the bf16 copy of the activation)."""
 
@@ -334,7 +334,7 @@ def encoder_forward_mx(P: Dict[str, torch.Tensor], cfg, ids: torch.Tensor, mask:
     """QST_PREC_FP8 oracle (inference): encoder_forward with every Linear computed on MXFP8 operands -- weights
     quantised from fp32; the layer input, the attention output and the LayerNorm-1 output quantised from their bf16
     copies; gelu(u) quantised from fp32 (it never exists in another format) -- and attention on bf16 operands, as the
-    HIP pipeline does (csrc/qst_api.hip forward_mx). train=True: the fp8 TRAINING forward (forward_mx_train) with the bf16
+    HIP pipeline does (csrc/qst_api.hip Pass::forward_fp8). train=True: the fp8 TRAINING forward (the same, training) with the bf16
     path's backward attached to every Linear (_LinearMxFwdBf16Bwd) -- autograd through the result is the oracle of
     "fp8 forward GEMMs, bf16 dgrad / wgrad". dropout (training only): an oracle/dropout_ref.Masks, applied at the four
     places encoder_forward applies it."""

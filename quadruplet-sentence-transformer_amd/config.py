@@ -9,7 +9,7 @@ Arena layout (one fp32 buffer for params, one for grads, two for Adam moments,
 one bf16 shadow for MFMA operands): every segment starts on a multiple of
 ARENA_ALIGN elements so that (a) 16-byte vector access is always aligned and
 (b) the fused AdamW kernel can look up weight-decay per 256-element chunk.
-The order below is a contract with csrc/qst_layout.h (qst_layout_build) and is
+The order below is a contract with csrc/qst_api.hip (build_layout) and is
 re-derived, not copied, on the C side; tests/test_layout.py checks both agree.
 """
 from __future__ import annotations
@@ -96,7 +96,7 @@ class Segment:
 
 
 def build_layout(cfg: EncoderConfig) -> Tuple[List[Segment], int]:
-    """Return (segments, total_elements). Mirrors qst_layout_build() in csrc/qst_layout.h."""
+    """Return (segments, total_elements). Mirrors build_layout() in csrc/qst_api.hip."""
     H, I, N = cfg.hidden_size, cfg.intermediate_size, cfg.num_layers
     segs: List[Segment] = []
     off = 0

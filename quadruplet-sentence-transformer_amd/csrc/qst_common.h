@@ -40,6 +40,23 @@ typedef __attribute__((ext_vector_type(8))) op16 op16x8;
 
 extern "C" int qst_set_hip_error(int code);
 
+// AdamW steps (optim.hip) behind the qst_clip_adamw_step* entry points of qst_api.hip
+extern "C" int qst_adamw_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                                const uint8_t* chunk_decay, int64_t n, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, float max_grad_norm, float grad_scale, int64_t step,
+                                float* norm_out, float* scratch, hipStream_t st);
+extern "C" int qst_adamw_launch_sched(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                                      const uint8_t* chunk_decay, int64_t n, float base_lr, float beta1, float beta2,
+                                      float eps, float weight_decay, float max_grad_norm, float grad_scale,
+                                      int64_t warmup_steps, int64_t total_steps, int64_t* step_dev, float* norm_out,
+                                      float* scratch, hipStream_t st);
+extern "C" int qst_adamw_launch_amp(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                                    const uint8_t* chunk_decay, int64_t n, float base_lr, float beta1, float beta2,
+                                    float eps, float weight_decay, float max_grad_norm, float grad_scale,
+                                    int64_t warmup_steps, int64_t total_steps, int64_t* step_dev, float* scaler_dev,
+                                    float growth, float backoff, int growth_interval, float* norm_out, float* scratch,
+                                    hipStream_t st);
+
 #define QST_HIP_CHECK(expr)                                 \
     do {                                                    \
         hipError_t _e = (expr);                             \
