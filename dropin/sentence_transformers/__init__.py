@@ -9,7 +9,7 @@ if _root not in _sys.path:
     _sys.path.insert(0, _root)
 
 from quadruplet_sentence_transformer_amd.sentence_transformer import InputExample, SentenceTransformer  # noqa: E402,F401
-from . import util, evaluation  # noqa: E402,F401
+from . import util, evaluation, models  # noqa: E402,F401
 
 
 class CrossEncoder:

@@ -1,0 +1,3 @@
+"""sentence_transformers.models: the Transformer / Pooling / Normalize descriptors that choose a head for a plain HF
+checkpoint (SentenceTransformer(modules=[...])). Every other module class of sentence-transformers is outside this build."""
+from quadruplet_sentence_transformer_amd.models import Normalize, Pooling, Transformer  # noqa: F401

@@ -121,7 +121,7 @@ int qst_refresh_shadow_mx(const qst_encoder* enc, const float* params, void* sha
  * over BertModel / MPNetModel.forward (transformers).
  *   ids, mask, type_ids : int64 [nseq, L] (type_ids may be NULL = all zero); L multiple of 32, <= 512
  *   params              : fp32 arena; shadow: bf16 arena from qst_refresh_shadow
- *   out_emb             : fp32 [nseq, H]  ('sentence_embedding')
+ *   out_emb             : fp32 [nseq, D]  ('sentence_embedding'; D = qst_encoder_embedding_dim, H for mean pooling)
  *   out_tok             : fp32 [nseq, L, H] token embeddings, or NULL
  *   saved               : activation arena (qst_encoder_saved_bytes)
  */
@@ -150,12 +150,28 @@ int qst_encoder_set_ffn_chain(qst_encoder* enc, int mask);
  * 128 x 384 where only that gives two: H = 768 from 32,768 token rows),
  * 1 = wherever such a kernel exists, 2 = never. Same results to fp32 summation order. */
 int qst_encoder_set_ln_fusion(qst_encoder* enc, int mode);
+/* The pooling head of this handle (ST models.Pooling): an OR of the QST_POOL_* bits below, concatenated in the fixed order
+ * cls, max, mean, mean_sqrt_len, weightedmean (include/qst_kernels.h: qst_pool_fwd has the exact semantics). 0 or
+ * QST_POOL_MEAN = mean pooling, the state of a new handle and the only head before version 101: qst_pool_norm_fwd/bwd,
+ * unchanged. Any other mode runs qst_pool_fwd/bwd. out_emb / grad_emb of qst_encoder_forward / _backward* are then
+ * [nseq, D] with D = qst_encoder_embedding_dim(); qst_encoder_saved_bytes grows by the pre-normalize D-vector and, with
+ * max, an int32 [nseq, H] argmax. A training forward records its mode with the arena: a backward of a handle set to
+ * another mode is refused (QST_ERR_BAD_ARG). */
+#define QST_POOL_CLS 1
+#define QST_POOL_MAX 2
+#define QST_POOL_MEAN 4
+#define QST_POOL_MEAN_SQRT 8
+#define QST_POOL_WMEAN 16
+#define QST_POOL_ALL 31
+int qst_encoder_set_pooling(qst_encoder* enc, int mode);
+/* D: the width of this handle's sentence embedding (hidden_size x number of pooling blocks). */
+int qst_encoder_embedding_dim(const qst_encoder* enc);
 int qst_dropout_advance(uint32_t* state_dev, void* stream);
 
 /*
  * Backward of the call above (replaces autograd through the same modules;
  * reference call site: `loss.backward()` inside SentenceTransformer.fit).
- *   grad_emb   : fp32 [nseq, H]
+ *   grad_emb   : fp32 [nseq, D]
  *   grads      : fp32 arena; gradients are ACCUMULATED into it (zero it for a fresh step)
  *   workspace  : qst_encoder_bwd_workspace_bytes
  *   saved      : the arena a TRAINING forward of this process filled (any handle of the same model and arena kind: the

@@ -259,6 +259,26 @@ int qst_pool_norm_fwd(const float* tok, const int64_t* mask, int nseq, int L, in
 int qst_pool_norm_bwd(const float* demb, const float* pooled, const int64_t* mask, int nseq, int L, int H,
                       int normalize, float* dtok, void* stream);
 
+/* Every ST 2.2.2 Pooling mode + optional Normalize, one launch per direction for any combination. mode = an OR of the
+ * QST_POOL_* bits; the enabled blocks are concatenated in the fixed order cls, max, mean, mean_sqrt_len, weightedmean
+ * (whatever order a caller names them in): emb / pooled f32 [nseq, D], D = (number of bits) * H, normalised over all of
+ * D. cls = row 0 (whatever its mask); max = per-column max over rows with mask != 0, padding counted as -1e9 (a sequence
+ * without a valid row pools to -1e9 and gets no gradient), ties to the LOWEST token index; mean = sum(m x) / max(sum m,
+ * 1e-9); mean_sqrt_len = sum(m x) / sqrt(max(sum m, 1e-9)); weightedmean = sum(m w x) / max(sum(m w), 1e-9), w_t = t + 1.
+ * pooled (pre-normalize) and argmax (int32 [nseq, H], the token row of each column's max; -1 = none) are what the
+ * backward reads; both may be NULL in an inference call. The backward writes every row of dtok f32 [nseq, L, H]; argmax
+ * is needed when mode has QST_POOL_MAX. H even, <= 1024; L <= 512. */
+#define QST_POOL_CLS 1
+#define QST_POOL_MAX 2
+#define QST_POOL_MEAN 4
+#define QST_POOL_MEAN_SQRT 8
+#define QST_POOL_WMEAN 16
+#define QST_POOL_ALL 31
+int qst_pool_fwd(const float* tok, const int64_t* mask, int nseq, int L, int H, int mode, int normalize,
+                 float* emb, float* pooled, int32_t* argmax, void* stream);
+int qst_pool_bwd(const float* demb, const float* pooled, const int32_t* argmax, const int64_t* mask, int nseq, int L, int H,
+                 int mode, int normalize, float* dtok, void* stream);
+
 /* Self-attention forward: qkv bf16 [nseq*L, 3H] token-major (q | k | v, heads concatenated),
  * mask int64 [nseq, L], rel_pos f32 [A, 2L] (qst_rel_pos_fwd: bias of relative position j - i at entry j - i + L)
  * or NULL -> ctx bf16 [nseq*L, H], lse f32 [nseq, A, L]. */

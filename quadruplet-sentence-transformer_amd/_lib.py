@@ -146,6 +146,8 @@ SIGNATURES = {
     "qst_forward_prologue": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "qst_pool_norm_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "qst_pool_norm_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "qst_pool_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "qst_pool_bwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "qst_attention_fwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "qst_attention_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "qst_attention_fwd_ex": (C.c_int, [C.POINTER(QstAttnDesc), vp]),
@@ -158,6 +160,8 @@ SIGNATURES = {
     "qst_encoder_set_dropout": (C.c_int, [vp, C.c_float, C.c_float, vp]),
     "qst_encoder_set_ffn_chain": (C.c_int, [vp, C.c_int]),
     "qst_encoder_set_ln_fusion": (C.c_int, [vp, C.c_int]),
+    "qst_encoder_set_pooling": (C.c_int, [vp, C.c_int]),
+    "qst_encoder_embedding_dim": (C.c_int, [vp]),
     "qst_transpose_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "qst_gelu_f32": (C.c_int, [vp, C.c_int64, vp, vp]),
     "qst_gelu_bwd_f32": (C.c_int, [vp, vp, C.c_int64, vp, vp]),

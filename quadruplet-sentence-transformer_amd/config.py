@@ -22,6 +22,25 @@ ARENA_ALIGN = 256  # elements
 ARCH_BERT = 0
 ARCH_MPNET = 1
 
+# sentence-transformers 2.2.2 models.Pooling modes, in the fixed order in which their [n, H] blocks are concatenated
+# (whatever order a caller names them in); bit i of the C-ABI's mode mask (include/qst.h QST_POOL_*) is POOLING_MODES[i]
+POOLING_MODES = ("cls", "max", "mean", "mean_sqrt_len", "weightedmean")
+
+
+def pooling_modes(pooling: str) -> Tuple[str, ...]:
+    """The modes of a pooling string ("cls", "max+mean", ...: '+'-joined names of POOLING_MODES) in the fixed order."""
+    names = [p.strip() for p in str(pooling).split("+")]
+    bad = [p for p in names if p not in POOLING_MODES]
+    if bad or not names:
+        raise ValueError(f"pooling {pooling!r}: unknown mode {bad[0] if bad else ''!r} (one of {POOLING_MODES}, "
+                         "or several joined with '+')")
+    return tuple(m for m in POOLING_MODES if m in names)
+
+
+def pooling_mask(pooling: str) -> int:
+    """QST_POOL_* bit mask of a pooling string (mean = 4)."""
+    return sum(1 << POOLING_MODES.index(m) for m in pooling_modes(pooling))
+
 
 @dataclass(frozen=True)
 class EncoderConfig:
@@ -39,10 +58,19 @@ class EncoderConfig:
     rel_buckets: int = 32           # MPNet only
     rel_max_distance: int = 128     # MPNet only
     pad_token_id: int = 0           # BERT 0, MPNet 1
+    pooling: str = "mean"           # ST `Pooling` modes: "cls", "max", "mean", "mean_sqrt_len", "weightedmean" or a '+' join
+
+    def __post_init__(self):
+        object.__setattr__(self, "pooling", "+".join(pooling_modes(self.pooling)))    # validated, in the fixed order
 
     @property
     def head_dim(self) -> int:
         return self.hidden_size // self.num_heads
+
+    @property
+    def embedding_dim(self) -> int:
+        """D: the width of the sentence embedding, hidden_size per pooling mode."""
+        return len(pooling_modes(self.pooling)) * self.hidden_size
 
     def to_dict(self) -> dict:
         return asdict(self)

@@ -15,7 +15,7 @@
 static thread_local int g_last_hip_error = 0;
 extern "C" int qst_set_hip_error(int code) { g_last_hip_error = code; return code; }
 extern "C" int qst_last_hip_error(void) { return g_last_hip_error; }
-extern "C" int qst_version(void) { return 100; }
+extern "C" int qst_version(void) { return 101; }
 
 extern "C" const char* qst_strerror(int s) {
     switch (s) {
@@ -114,13 +114,14 @@ namespace {
 enum { ARENA_BF16 = 0, ARENA_X3 = 1, ARENA_F16 = 2 };   // the bf16 activation arena (bf16 and fp8 forwards) / the fp32 one of bf16x3 / the f16 one
 // A record also holds the shape of its forward: an arena whose address was reused by a later allocation of another shape (or a
 // backward called with another nseq / L than its forward) is refused instead of read with the wrong plan.
-struct FwdRec { uint32_t hidden = 0, attn = 0; int kind = ARENA_BF16; uint64_t seq = 0; int nseq = 0, L = 0; };
+// ... and its pooling head (qst_encoder_set_pooling): the saved pre-normalize vector and argmax are laid out for that mode.
+struct FwdRec { uint32_t hidden = 0, attn = 0; int kind = ARENA_BF16; uint64_t seq = 0; int nseq = 0, L = 0, pool = QST_POOL_MEAN; };
 std::mutex g_rec_mu;
 std::unordered_map<const void*, FwdRec> g_recs;
 uint64_t g_rec_seq = 0;
-void rec_put(const void* saved, uint32_t hidden, uint32_t attn, int kind, int nseq, int L) {
+void rec_put(const void* saved, uint32_t hidden, uint32_t attn, int kind, int nseq, int L, int pool) {
     std::lock_guard<std::mutex> lk(g_rec_mu);
-    g_recs[saved] = FwdRec{hidden, attn, kind, ++g_rec_seq, nseq, L};
+    g_recs[saved] = FwdRec{hidden, attn, kind, ++g_rec_seq, nseq, L, pool};
     if (g_recs.size() > 4096) {
         // arenas that were freed long ago: keep the 2048 most recently WRITTEN records (by count -- a cut at "sequence number -
         // 2048" dropped live arenas once hot ones had been re-put often enough)
@@ -159,6 +160,7 @@ struct qst_encoder {
     // that wait on the LDS-DMA stream, and stores and DMAs retire through one in-order counter.
     int ffn_chain = 1;
     int ln_fusion = 0;      // qst_encoder_set_ln_fusion: 0 = by size, 1 = wherever a fused kernel exists, 2 = never
+    int pool = QST_POOL_MEAN;   // qst_encoder_set_pooling: QST_POOL_* bits; mean alone runs the original pool_norm kernels
 };
 
 extern "C" int64_t qst_arena_elems(const qst_config* cfg) { return cfg_ok(cfg) ? build_layout(cfg).total : QST_ERR_BAD_ARG; }
@@ -281,13 +283,21 @@ struct LayerAct {
     size_t qkv, lse, ctx, y1, y1b, xh1, rs1, u, hact, x, xb, xh2, rs2;   // x/xb/xh2/rs2 = layer OUTPUT
 };
 struct ActPlan {
-    size_t pos_ids, x0, x0b, xh0, rs0, s_scratch, pooled, rel;
+    size_t pos_ids, x0, x0b, xh0, rs0, s_scratch, pooled, rel, argmax;
     size_t dropst;          // uint32[4]: the dropout counter as THIS forward used it (backward rebuilds the masks from it)
     std::vector<LayerAct> layers;
     size_t total;
 };
 
-ActPlan plan_acts(const qst_config& c, int nseq, int L, bool training) {
+// The pooling head's part of an activation arena: the pre-normalize [nseq, D] vector (D = H for mean pooling, where the
+// arena is what it always was) and, for a head with max, the int32 [nseq, H] argmax -- placed last, so that every other
+// offset is the same for every head.
+size_t pool_dim(const qst_config& c, int pool) { return (size_t)__builtin_popcount((unsigned)pool) * c.hidden_size; }
+size_t take_argmax(Bump& take, const qst_config& c, int nseq, int pool) {
+    return (pool & QST_POOL_MAX) ? take((size_t)nseq * c.hidden_size * 4) : 0;
+}
+
+ActPlan plan_acts(const qst_config& c, int nseq, int L, bool training, int pool) {
     ActPlan p;
     const size_t M = (size_t)nseq * L, H = c.hidden_size, I = c.intermediate_size, A = c.num_heads;
     Bump take;
@@ -295,7 +305,7 @@ ActPlan plan_acts(const qst_config& c, int nseq, int L, bool training) {
     p.dropst = take(16);
     p.x0 = take(M * H * 4); p.x0b = take(M * H * 2); p.xh0 = take(M * H * 2); p.rs0 = take(M * 4);
     p.s_scratch = take(M * H * 4);
-    p.pooled = take((size_t)nseq * H * 4);
+    p.pooled = take((size_t)nseq * pool_dim(c, pool) * 4);
     p.rel = (c.arch == QST_ARCH_MPNET) ? take(A * (size_t)2 * L * 4) : 0;      // relative-position vectors [A][2L]
     p.layers.resize(c.num_layers);
     for (int l = 0; l < c.num_layers; ++l) {
@@ -309,13 +319,14 @@ ActPlan plan_acts(const qst_config& c, int nseq, int L, bool training) {
             a = p.layers[l - 2];      // inference: ping-pong two layer slots (a layer reads the previous slot's x)
         }
     }
+    p.argmax = take_argmax(take, c, nseq, pool);
     p.total = take.off;
     return p;
 }
 
 // QST_PREC_BF16X3 forward: fp32 activations, inference only (two residual slots ping-pong)
-struct X3Plan { size_t pos_ids, x[2], qkv, ctx, s, y1, h, pooled, rel, total; };
-X3Plan plan_x3(const qst_config& c, int nseq, int L) {
+struct X3Plan { size_t pos_ids, x[2], qkv, ctx, s, y1, h, pooled, rel, argmax, total; };
+X3Plan plan_x3(const qst_config& c, int nseq, int L, int pool) {
     X3Plan p;
     const size_t M = (size_t)nseq * L, H = c.hidden_size, I = c.intermediate_size, A = c.num_heads;
     Bump take;
@@ -323,8 +334,9 @@ X3Plan plan_x3(const qst_config& c, int nseq, int L) {
     p.x[0] = take(M * H * 4); p.x[1] = take(M * H * 4);
     p.qkv = take(M * 3 * H * 4); p.ctx = take(M * H * 4); p.s = take(M * H * 4); p.y1 = take(M * H * 4);
     p.h = take(M * I * 4);
-    p.pooled = take((size_t)nseq * H * 4);
+    p.pooled = take((size_t)nseq * pool_dim(c, pool) * 4);
     p.rel = (c.arch == QST_ARCH_MPNET) ? take(A * (size_t)L * L * 4) : 0;
+    p.argmax = take_argmax(take, c, nseq, pool);
     p.total = take.off;
     return p;
 }
@@ -333,21 +345,22 @@ X3Plan plan_x3(const qst_config& c, int nseq, int L) {
 // runs, 4x the bf16 path's activation bytes). s0 / s1 / s2 are the PRE-norm inputs of the three LayerNorms (the backward
 // recomputes mean and rstd from them), u the pre-GELU tensor.
 struct X3Layer { size_t qkv, ctx, s1, y1, u, h, s2, x; };
-struct X3TrainPlan { size_t pos_ids, dropst, s0, x0, pooled, rel, total; std::vector<X3Layer> layers; };
-X3TrainPlan plan_x3_train(const qst_config& c, int nseq, int L) {
+struct X3TrainPlan { size_t pos_ids, dropst, s0, x0, pooled, rel, argmax, total; std::vector<X3Layer> layers; };
+X3TrainPlan plan_x3_train(const qst_config& c, int nseq, int L, int pool) {
     X3TrainPlan p;
     const size_t M = (size_t)nseq * L, H = c.hidden_size, I = c.intermediate_size, A = c.num_heads;
     Bump take;
     p.pos_ids = take(M * 4);
     p.dropst = take(16);                               // the dropout state {seed, step} this forward ran under
     p.s0 = take(M * H * 4); p.x0 = take(M * H * 4);
-    p.pooled = take((size_t)nseq * H * 4);
+    p.pooled = take((size_t)nseq * pool_dim(c, pool) * 4);
     p.rel = (c.arch == QST_ARCH_MPNET) ? take(A * (size_t)L * L * 4) : 0;
     p.layers.resize(c.num_layers);
     for (auto& a : p.layers) {
         a.qkv = take(M * 3 * H * 4); a.ctx = take(M * H * 4); a.s1 = take(M * H * 4); a.y1 = take(M * H * 4);
         a.u = take(M * I * 4); a.h = take(M * I * 4); a.s2 = take(M * H * 4); a.x = take(M * H * 4);
     }
+    p.argmax = take_argmax(take, c, nseq, pool);
     p.total = take.off;
     return p;
 }
@@ -368,8 +381,8 @@ X3BwdPlan plan_x3_bwd(const qst_config& c, int nseq, int L) {
 }
 
 // QST_PREC_FP8 forward (inference): MXFP8 operands for every Linear, bf16 attention, fp32 residual stream / LayerNorm
-struct MxPlan { size_t pos_ids, x[2], xb, xq, xs, qkv, ctx, cq, cs, s, y1, y1b, yq, ys, hq, hs, pooled, rel, total; };
-MxPlan plan_mx(const qst_config& c, int nseq, int L) {
+struct MxPlan { size_t pos_ids, x[2], xb, xq, xs, qkv, ctx, cq, cs, s, y1, y1b, yq, ys, hq, hs, pooled, rel, argmax, total; };
+MxPlan plan_mx(const qst_config& c, int nseq, int L, int pool) {
     MxPlan p;
     const size_t M = (size_t)nseq * L, H = c.hidden_size, I = c.intermediate_size, A = c.num_heads;
     Bump take;
@@ -379,8 +392,9 @@ MxPlan plan_mx(const qst_config& c, int nseq, int L) {
     p.qkv = take(M * 3 * H * 2); p.ctx = take(M * H * 2); p.cq = take(M * H); p.cs = take(M * H / 32);
     p.s = take(M * H * 4); p.y1 = take(M * H * 4); p.y1b = take(M * H * 2); p.yq = take(M * H); p.ys = take(M * H / 32);
     p.hq = take(M * I); p.hs = take(M * I / 32);
-    p.pooled = take((size_t)nseq * H * 4);
+    p.pooled = take((size_t)nseq * pool_dim(c, pool) * 4);
     p.rel = (c.arch == QST_ARCH_MPNET) ? take(A * (size_t)2 * L * 4) : 0;
+    p.argmax = take_argmax(take, c, nseq, pool);
     p.total = take.off;
     return p;
 }
@@ -436,6 +450,14 @@ extern "C" int qst_encoder_set_ln_fusion(qst_encoder* e, int mode) {
     e->ln_fusion = mode;
     return QST_OK;
 }
+extern "C" int qst_encoder_set_pooling(qst_encoder* e, int mode) {
+    if (!e || mode < 0 || mode > QST_POOL_ALL) return QST_ERR_BAD_ARG;
+    e->pool = mode ? mode : QST_POOL_MEAN;
+    return QST_OK;
+}
+extern "C" int qst_encoder_embedding_dim(const qst_encoder* e) {
+    return e ? (int)pool_dim(e->cfg, e->pool) : QST_ERR_BAD_ARG;
+}
 extern "C" int qst_encoder_set_dropout(qst_encoder* e, float p_hidden, float p_attn, uint32_t* state_dev) {
     if (!e || !(p_hidden >= 0.f && p_hidden < 1.f) || !(p_attn >= 0.f && p_attn < 1.f)) return QST_ERR_BAD_ARG;
     if ((p_hidden > 0.f || p_attn > 0.f) && !state_dev) return QST_ERR_BAD_ARG;
@@ -447,11 +469,13 @@ extern "C" int qst_encoder_set_dropout(qst_encoder* e, float p_hidden, float p_a
 
 extern "C" size_t qst_encoder_saved_bytes(const qst_encoder* e, int nseq, int L, int training) {
     if (shape_ok(e, nseq, L) != QST_OK) return 0;
-    if (e->cfg.precision == QST_PREC_BF16X3) return training ? plan_x3_train(e->cfg, nseq, L).total : plan_x3(e->cfg, nseq, L).total;
+    const int pool = e->pool;
+    if (e->cfg.precision == QST_PREC_BF16X3)
+        return training ? plan_x3_train(e->cfg, nseq, L, pool).total : plan_x3(e->cfg, nseq, L, pool).total;
     if (e->cfg.precision == QST_PREC_FP8)
-        return training ? plan_mx_train_operands(e->cfg, nseq, L, plan_acts(e->cfg, nseq, L, true).total).total
-                        : plan_mx(e->cfg, nseq, L).total;
-    return plan_acts(e->cfg, nseq, L, training != 0).total;
+        return training ? plan_mx_train_operands(e->cfg, nseq, L, plan_acts(e->cfg, nseq, L, true, pool).total).total
+                        : plan_mx(e->cfg, nseq, L, pool).total;
+    return plan_acts(e->cfg, nseq, L, training != 0, pool).total;
 }
 extern "C" size_t qst_encoder_bwd_workspace_bytes(const qst_encoder* e, int nseq, int L) {
     if (shape_ok(e, nseq, L) != QST_OK) return 0;
@@ -569,7 +593,7 @@ struct Pass {
         pos_ids = (const int32_t*)(sv + pos_off);
         QST_TRY(qst_forward_prologue(ids, nseq, L, c.arch, c.pad_token_id, (int32_t*)(sv + pos_off),
                                      dropping ? e->drop_state : nullptr, drop_state, st));
-        if (training) rec_put(sv, thr_hidden, thr_attn, kind, nseq, L);
+        if (training) rec_put(sv, thr_hidden, thr_attn, kind, nseq, L, e->pool);
         return QST_OK;
     }
     // MPNet: the relative-position table (qst_rel_pos_fwd for the bf16 attention, qst_rel_bias_fwd for bf16x3)
@@ -584,10 +608,25 @@ struct Pass {
         q.drop = probs(QST_DROP_SITE_PROBS(l));
         return q;
     }
-    // pooling (+ normalisation) into out_emb, and the token states into out_tok when asked for
-    int tail(const float* x, size_t pooled, float* out_emb, float* out_tok) const {
-        QST_TRY(qst_pool_norm_fwd(x, mask, nseq, L, H, c.normalize, out_emb, F(pooled), st));
+    // pooling (+ normalisation) into out_emb, and the token states into out_tok when asked for. Mean pooling alone runs
+    // the original kernel pair (pool_norm_fwd/bwd), every other head qst_pool_fwd/bwd.
+    int tail(const float* x, size_t pooled, size_t argmax, float* out_emb, float* out_tok) const {
+        if (e->pool == QST_POOL_MEAN) QST_TRY(qst_pool_norm_fwd(x, mask, nseq, L, H, c.normalize, out_emb, F(pooled), st));
+        else QST_TRY(qst_pool_fwd(x, mask, nseq, L, H, e->pool, c.normalize, out_emb, F(pooled), argmax_at(argmax), st));
         if (out_tok) QST_HIP_CHECK(hipMemcpyAsync(out_tok, x, (size_t)M * H * 4, hipMemcpyDeviceToDevice, st));
+        return QST_OK;
+    }
+
+    int32_t* argmax_at(size_t off) const { return (e->pool & QST_POOL_MAX) ? (int32_t*)(sv + off) : nullptr; }
+    int head_bwd(const float* grad_emb, size_t pooled, size_t argmax, float* dtok) const {
+        if (e->pool == QST_POOL_MEAN) return qst_pool_norm_bwd(grad_emb, F(pooled), mask, nseq, L, H, c.normalize, dtok, st);
+        return qst_pool_bwd(grad_emb, F(pooled), argmax_at(argmax), mask, nseq, L, H, e->pool, c.normalize, dtok, st);
+    }
+    // a backward over an arena that a training forward of ANOTHER pooling head filled is refused (its saved vector and
+    // argmax are laid out for that head); an arena no forward has filled is left to backward_dropout (QST_ERR_NO_FORWARD)
+    int check_pool(int kind) const {
+        FwdRec fr;
+        if (rec_get(sv, kind, nseq, L, &fr) && fr.pool != e->pool) return QST_ERR_BAD_ARG;
         return QST_OK;
     }
 
@@ -629,7 +668,7 @@ struct Pass {
 
 // The 16-bit forward (QST_PREC_BF16 / F16 / F16W)
 int Pass::forward_op16(const void* shadow, float* out_emb, float* out_tok, size_t saved_bytes, bool training) {
-    const ActPlan p = plan_acts(c, nseq, L, training);
+    const ActPlan p = plan_acts(c, nseq, L, training, e->pool);
     if (saved_bytes < p.total) return QST_ERR_WORKSPACE;
     const uint16_t* sh = (const uint16_t*)shadow;          // bf16, or IEEE half on a QST_PREC_F16 handle
     auto W = [&](int seg) { return sh + lay.segs[seg].shadow_off; };
@@ -693,7 +732,7 @@ int Pass::forward_op16(const void* shadow, float* out_emb, float* out_tok, size_
         x = F(a.x);
         xb = sv + a.xb;
     }
-    return tail(x, p.pooled, out_emb, out_tok);
+    return tail(x, p.pooled, p.argmax, out_emb, out_tok);
 }
 
 // fp8 matrix-core forward (QST_PREC_FP8; BASELINE configs[4]): the operator sequence of the bf16 forward with every
@@ -706,8 +745,8 @@ int Pass::forward_op16(const void* shadow, float* out_emb, float* out_tok, size_
 // training forward. The backward is then qst_encoder_backward_stage as it is, on the bf16 shadows: fp8 forward GEMMs, bf16
 // dgrad / wgrad from fp32 master weights. The MXFP8 operand copies live behind the arena.
 int Pass::forward_fp8(const void* shadow, float* out_emb, float* out_tok, size_t saved_bytes, bool training) {
-    const ActPlan p = training ? plan_acts(c, nseq, L, true) : ActPlan{};
-    const MxPlan pm = training ? MxPlan{} : plan_mx(c, nseq, L);
+    const ActPlan p = training ? plan_acts(c, nseq, L, true, e->pool) : ActPlan{};
+    const MxPlan pm = training ? MxPlan{} : plan_mx(c, nseq, L, e->pool);
     const MxOperands mq = training ? plan_mx_train_operands(c, nseq, L, p.total)
                                    : MxOperands{pm.xq, pm.xs, pm.cq, pm.cs, pm.yq, pm.ys, pm.hq, pm.hs, pm.total};
     if (saved_bytes < mq.total) return QST_ERR_WORKSPACE;
@@ -797,13 +836,13 @@ int Pass::forward_fp8(const void* shadow, float* out_emb, float* out_tok, size_t
         }
         x = xn;
     }
-    return tail(x, training ? p.pooled : pm.pooled, out_emb, out_tok);
+    return tail(x, training ? p.pooled : pm.pooled, training ? p.argmax : pm.argmax, out_emb, out_tok);
 }
 
 // Parity-precision forward (QST_PREC_BF16X3): same operator sequence as the bf16 forward on fp32 activations and the fp32
 // master weights, contractions through split-bf16 x3 MFMA kernels (csrc/x3.hip).
 int Pass::forward_x3(float* out_emb, float* out_tok, size_t saved_bytes) {
-    const X3Plan p = plan_x3(c, nseq, L);
+    const X3Plan p = plan_x3(c, nseq, L, e->pool);
     if (saved_bytes < p.total) return QST_ERR_WORKSPACE;
     const float eps = c.layer_norm_eps;
     QST_TRY(prologue(p.pos_ids, false, ARENA_X3));
@@ -824,12 +863,12 @@ int Pass::forward_x3(float* out_emb, float* out_tok, size_t saved_bytes) {
         QST_TRY(qst_ln_fwd(s, P(b + LN2_G), P(b + LN2_B), eps, M, H, xn, nullptr, nullptr, nullptr, st));
         x = xn;
     }
-    return tail(x, p.pooled, out_emb, out_tok);
+    return tail(x, p.pooled, p.argmax, out_emb, out_tok);
 }
 
 // QST_PREC_BF16X3 training forward: the same arithmetic as forward_x3, every intermediate kept (X3TrainPlan)
 int Pass::forward_x3_train(float* out_emb, float* out_tok, size_t saved_bytes) {
-    const X3TrainPlan p = plan_x3_train(c, nseq, L);
+    const X3TrainPlan p = plan_x3_train(c, nseq, L, e->pool);
     if (saved_bytes < p.total) return QST_ERR_WORKSPACE;
     const float eps = c.layer_norm_eps;
     // dropout as the bf16 training forward has it (same sites, same counter-based masks, the snapshot beside the activations);
@@ -863,7 +902,7 @@ int Pass::forward_x3_train(float* out_emb, float* out_tok, size_t saved_bytes) {
         QST_TRY(qst_ln_fwd(F(a.s2), P(b + LN2_G), P(b + LN2_B), eps, M, H, F(a.x), nullptr, nullptr, nullptr, st));
         x = F(a.x);
     }
-    return tail(x, p.pooled, out_emb, out_tok);
+    return tail(x, p.pooled, p.argmax, out_emb, out_tok);
 }
 
 // ... and its backward: fp32-class gradients ACCUMULATED into `grads`. Every contraction runs on split-bf16 x3 products: a
@@ -872,7 +911,7 @@ int Pass::forward_x3_train(float* out_emb, float* out_tok, size_t saved_bytes) {
 // lives in the workspace between calls), so that a data-parallel step can hand a finished layer's gradients to the all-reduce
 // while the layers below are still running (round 5; rounds 3-4 ran it as one call and reduced afterwards).
 int Pass::backward_x3(const float* grad_emb, size_t saved_bytes, size_t workspace_bytes, int flags, int layer_hi, int layer_lo) {
-    const X3TrainPlan p = plan_x3_train(c, nseq, L);
+    const X3TrainPlan p = plan_x3_train(c, nseq, L, e->pool);
     const X3BwdPlan w = plan_x3_bwd(c, nseq, L);
     if (saved_bytes < p.total || workspace_bytes < w.total) return QST_ERR_WORKSPACE;
     // dropout: the masks of the forward that filled `saved` (its thresholds from its record, its (seed, step) from the
@@ -908,7 +947,7 @@ int Pass::backward_x3(const float* grad_emb, size_t saved_bytes, size_t workspac
         drel = Wk(w.drel);
         if (flags & QST_BWD_HEAD) QST_HIP_CHECK(hipMemsetAsync(drel, 0, (size_t)A * L * L * 4, st));
     }
-    if (flags & QST_BWD_HEAD) QST_TRY(qst_pool_norm_bwd(grad_emb, F(p.pooled), mask, nseq, L, H, c.normalize, dx, st));
+    if (flags & QST_BWD_HEAD) QST_TRY(head_bwd(grad_emb, p.pooled, p.argmax, dx));
     for (int l = layer_hi - 1; l >= layer_lo; --l) {
         const int b = lay.layer0[l];
         const X3Layer& a = p.layers[l];
@@ -944,7 +983,7 @@ int Pass::backward_x3(const float* grad_emb, size_t saved_bytes, size_t workspac
 // = the bf16 shadows)
 int Pass::backward_op16(const void* shadow, const float* grad_emb, size_t saved_bytes, size_t workspace_bytes, int flags,
                         int layer_hi, int layer_lo) {
-    const ActPlan p = plan_acts(c, nseq, L, true);
+    const ActPlan p = plan_acts(c, nseq, L, true, e->pool);
     const BwdPlan w = plan_bwd(c, nseq, L);
     if (saved_bytes < p.total || workspace_bytes < w.total) return QST_ERR_WORKSPACE;
     const uint16_t* sh = (const uint16_t*)shadow;
@@ -984,7 +1023,7 @@ int Pass::backward_op16(const void* shadow, const float* grad_emb, size_t saved_
         rel = F(p.rel);
         if (flags & QST_BWD_HEAD) QST_HIP_CHECK(hipMemsetAsync(drel, 0, (size_t)A * 2 * L * 4, st));
     }
-    if (flags & QST_BWD_HEAD) QST_TRY(qst_pool_norm_bwd(grad_emb, F(p.pooled), mask, nseq, L, H, c.normalize, dxa, st));
+    if (flags & QST_BWD_HEAD) QST_TRY(head_bwd(grad_emb, p.pooled, p.argmax, dxa));
     // all four weight gradients (+ bias gradients) of a layer in one grouped launch
     auto wgrad = [&](int l) -> int {
         const LayerAct& a = p.layers[l];
@@ -1150,6 +1189,7 @@ extern "C" int qst_encoder_backward_stage(qst_encoder* e, const int64_t* ids, co
     Pass ps(e, ids, mask, type_ids, nseq, L, params, saved, stream, false);
     ps.ws = (char*)workspace;
     ps.grads = grads;
+    QST_TRY(ps.check_pool(x3 ? ARENA_X3 : ps.ops.arena_kind));
     if (x3) return ps.backward_x3(grad_emb, saved_bytes, workspace_bytes, flags, layer_hi, layer_lo);
     return ps.backward_op16(shadow, grad_emb, saved_bytes, workspace_bytes, flags, layer_hi, layer_lo);
 }

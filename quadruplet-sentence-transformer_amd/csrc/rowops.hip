@@ -519,6 +519,301 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_norm_bwd_kernel(const fl
     }
 }
 
+// Every pooling mode of sentence-transformers 2.2.2 models.Pooling + optional Normalize, one launch for any combination:
+// the enabled blocks of [cls | max | mean | mean_sqrt_len | weightedmean] (QST_POOL_* bits 0..4, always in this order)
+// are concatenated into a D = k * H vector per sequence and normalised over all of D. Layout of pool_norm_fwd_kernel:
+// one workgroup of 8 waves per sequence, a wave takes every 8th token row, a lane two columns per 64 (8-byte accesses);
+// rows of padding are not read, and a head without max / mean-like blocks (pure cls) reads row 0 only. The cross-wave
+// reduction goes through [8][H] floats of LDS, one quantity after the other (max adds [8][H] ints for its argmax). The
+// D-vector never goes through LDS: each thread keeps its two columns of every block in registers, so D = 5 * 1024 needs
+// no more LDS than H = 1024 (64 KiB with max).
+// max: padding rows count as -1e9 (ST fills them in place before torch.max), so a sequence with no valid token pools to
+// -1e9 in every column and its argmax is -1 (no gradient); ties go to the LOWEST token index.
+constexpr int POOL_NMODES = 5;
+__global__ __launch_bounds__(64 * POOL_WAVES) void pool_fwd_kernel(const float* tok, const int64_t* mask, int L, int H, int mode,
+                                                                   int normalize, float* emb, float* pooled, int32_t* argmax) {
+    __shared__ float red[POOL_WAVES];
+    __shared__ float msk[512];
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [POOL_WAVES][H] floats, then (max) [POOL_WAVES][H] ints
+    float* part = (float*)smem;
+    int* pidx = (int*)(part + POOL_WAVES * H);
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nv = H >> 1;
+    const bool want_max = (mode & QST_POOL_MAX) != 0;
+    const bool want_sum = (mode & (QST_POOL_MEAN | QST_POOL_MEAN_SQRT)) != 0, want_w = (mode & QST_POOL_WMEAN) != 0;
+    const bool rows = want_max || want_sum || want_w;                // (uniform)
+    const float* seq = tok + (size_t)s * L * H;
+    float cnt = 0.f, wcnt = 0.f, npad = 0.f;
+    if (rows) {
+        for (int t = tid; t < L; t += 64 * POOL_WAVES) msk[t] = (float)mask[(size_t)s * L + t];
+        __syncthreads();
+        for (int t = 0; t < L; ++t) {
+            const float m = msk[t];
+            cnt += m;
+            wcnt += m * (float)(t + 1);
+            npad += m == 0.f ? 1.f : 0.f;
+        }
+    }
+    const float mx0 = npad > 0.f ? -1e9f : -INFINITY;
+    f32x2 as[POOL_VPL], aw[POOL_VPL], mx[POOL_VPL];
+    int ix[POOL_VPL][2];
+#pragma unroll
+    for (int i = 0; i < POOL_VPL; ++i) {
+        as[i][0] = as[i][1] = aw[i][0] = aw[i][1] = 0.f;
+        mx[i][0] = mx[i][1] = mx0;
+        ix[i][0] = ix[i][1] = -1;
+    }
+    if (rows) {
+        // four rows of this wave in flight at a time, in increasing token order (a strict > keeps the first maximum)
+        for (int t0 = wave; t0 < L; t0 += 4 * POOL_WAVES) {
+            f32x2 v[4][POOL_VPL];
+            float m[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int t = t0 + u * POOL_WAVES;
+                m[u] = t < L ? msk[t] : 0.f;
+                const float* row = seq + (size_t)(t < L ? t : 0) * H;
+#pragma unroll
+                for (int i = 0; i < POOL_VPL; ++i) {
+                    const int c = lane + 64 * i;
+                    v[u][i][0] = v[u][i][1] = 0.f;
+                    if (c < nv && m[u] != 0.f) v[u][i] = *(const f32x2*)(row + 2 * c);       // (m: uniform)
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int t = t0 + u * POOL_WAVES;
+                const float wt = m[u] * (float)(t + 1);
+#pragma unroll
+                for (int i = 0; i < POOL_VPL; ++i) {
+                    as[i] += v[u][i] * m[u];
+                    aw[i] += v[u][i] * wt;
+                    if (want_max && m[u] != 0.f) {
+#pragma unroll
+                        for (int h = 0; h < 2; ++h)
+                            if (v[u][i][h] > mx[i][h]) { mx[i][h] = v[u][i][h]; ix[i][h] = t; }
+                    }
+                }
+            }
+        }
+    }
+    // cross-wave sums: the thread's columns c = tid + 512 k
+    auto stage = [&](const f32x2 (&a)[POOL_VPL]) {
+#pragma unroll
+        for (int i = 0; i < POOL_VPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nv) *(f32x2*)(part + wave * H + 2 * c) = a[i];
+        }
+    };
+    auto colsum = [&](float (&out)[2]) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 64 * POOL_WAVES * k;
+            out[k] = 0.f;
+            if (c < H) {
+#pragma unroll
+                for (int w = 0; w < POOL_WAVES; ++w) out[k] += part[w * H + c];
+            }
+        }
+    };
+    float e[POOL_NMODES][2];
+#pragma unroll
+    for (int j = 0; j < POOL_NMODES; ++j) e[j][0] = e[j][1] = 0.f;
+    if (want_sum) {
+        stage(as);
+        __syncthreads();
+        float sm[2];
+        colsum(sm);
+        const float inv = 1.0f / fmaxf(cnt, 1e-9f), rs = sqrtf(fmaxf(cnt, 1e-9f));
+#pragma unroll
+        for (int k = 0; k < 2; ++k) { e[2][k] = sm[k] * inv; e[3][k] = sm[k] / rs; }
+        __syncthreads();
+    }
+    if (want_w) {
+        stage(aw);
+        __syncthreads();
+        float sw[2];
+        colsum(sw);
+        const float wd = fmaxf(wcnt, 1e-9f);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) e[4][k] = sw[k] / wd;
+        __syncthreads();
+    }
+    if (want_max) {
+#pragma unroll
+        for (int i = 0; i < POOL_VPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nv) {
+                *(f32x2*)(part + wave * H + 2 * c) = mx[i];
+                pidx[wave * H + 2 * c] = ix[i][0];
+                pidx[wave * H + 2 * c + 1] = ix[i][1];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 64 * POOL_WAVES * k;
+            if (c < H) {
+                float best = part[c];
+                int bi = pidx[c];
+#pragma unroll
+                for (int w = 1; w < POOL_WAVES; ++w) {
+                    const float v = part[w * H + c];
+                    const int j = pidx[w * H + c];
+                    // the greater value; on a tie the lower token index (a wave without a valid row has index -1)
+                    if (v > best || (v == best && j >= 0 && (bi < 0 || j < bi))) { best = v; bi = j; }
+                }
+                e[1][k] = best;
+                if (argmax) argmax[(size_t)s * H + c] = bi;
+            }
+        }
+    }
+    if (mode & QST_POOL_CLS) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 64 * POOL_WAVES * k;
+            if (c < H) e[0][k] = seq[c];                      // row 0, whatever its mask
+        }
+    }
+    const int D = __popc(mode & 31) * H;
+    float sq = 0.f;
+    int o = 0;
+#pragma unroll
+    for (int j = 0; j < POOL_NMODES; ++j) {
+        if (!(mode & (1 << j))) continue;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 64 * POOL_WAVES * k;
+            if (c < H) {
+                sq += e[j][k] * e[j][k];
+                if (pooled) pooled[(size_t)s * D + o * H + c] = e[j][k];
+            }
+        }
+        ++o;
+    }
+    sq = wave_sum(sq);
+    if (lane == 0) red[wave] = sq;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < POOL_WAVES; ++w) tot += red[w];
+    const float sc = normalize ? 1.0f / fmaxf(sqrtf(tot), 1e-12f) : 1.0f;
+    o = 0;
+#pragma unroll
+    for (int j = 0; j < POOL_NMODES; ++j) {
+        if (!(mode & (1 << j))) continue;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 64 * POOL_WAVES * k;
+            if (c < H) emb[(size_t)s * D + o * H + c] = e[j][k] * sc;
+        }
+        ++o;
+    }
+}
+
+// Its backward: the normalisation backward over the whole D-vector, then every token row of dtok [L, H] written once:
+// row t = m_t * (a + (t + 1) * b) [+ d(cls) on row 0] [+ d(max) in the columns whose argmax is t], with
+// a = d(mean) / count + d(mean_sqrt_len) / sqrt(count) and b = d(weightedmean) / sum(m * w). Rows that receive nothing
+// (padding, and every row of a pure-cls head but row 0) are written as zeros.
+__global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(const float* demb, const float* pooled, const int32_t* argmax,
+                                                                   const int64_t* mask, int L, int H, int mode, int normalize,
+                                                                   float* dtok) {
+    __shared__ float red[2 * POOL_WAVES];
+    __shared__ float msk[512];
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [H] floats each: a, b, d(cls), d(max); [H] ints: argmax
+    float* ga = (float*)smem;
+    float* gb = ga + H;
+    float* gc = gb + H;
+    float* gm = gc + H;
+    int* am = (int*)(gm + H);
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nv = H >> 1;
+    const bool want_max = (mode & QST_POOL_MAX) != 0, want_cls = (mode & QST_POOL_CLS) != 0;
+    for (int t = tid; t < L; t += 64 * POOL_WAVES) msk[t] = (float)mask[(size_t)s * L + t];
+    __syncthreads();
+    float cnt = 0.f, wcnt = 0.f;
+    for (int t = 0; t < L; ++t) { cnt += msk[t]; wcnt += msk[t] * (float)(t + 1); }
+    const int D = __popc(mode & 31) * H;
+    float e[POOL_NMODES][2], g[POOL_NMODES][2];
+    float sq = 0.f, dot = 0.f;
+    int o = 0;
+#pragma unroll
+    for (int j = 0; j < POOL_NMODES; ++j) {
+        e[j][0] = e[j][1] = g[j][0] = g[j][1] = 0.f;
+        if (!(mode & (1 << j))) continue;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = tid + 64 * POOL_WAVES * k;
+            if (c < H) {
+                e[j][k] = pooled[(size_t)s * D + o * H + c];
+                g[j][k] = demb[(size_t)s * D + o * H + c];
+                sq += e[j][k] * e[j][k];
+                dot += e[j][k] * g[j][k];
+            }
+        }
+        ++o;
+    }
+    sq = wave_sum(sq); dot = wave_sum(dot);
+    if (lane == 0) { red[wave] = sq; red[POOL_WAVES + wave] = dot; }
+    __syncthreads();
+    sq = 0.f; dot = 0.f;
+#pragma unroll
+    for (int w = 0; w < POOL_WAVES; ++w) { sq += red[w]; dot += red[POOL_WAVES + w]; }
+    const float nrm = sqrtf(sq);
+    const float inv = 1.0f / fmaxf(cnt, 1e-9f), rs = sqrtf(fmaxf(cnt, 1e-9f)), wd = fmaxf(wcnt, 1e-9f);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = tid + 64 * POOL_WAVES * k;
+        if (c < H) {
+            float dp[POOL_NMODES];
+#pragma unroll
+            for (int j = 0; j < POOL_NMODES; ++j) {
+                dp[j] = g[j][k];
+                if (normalize) {
+                    // y = e / max(n, eps): dy/de = (I - e e^T / n^2) / n for n > eps, I/eps otherwise
+                    if (nrm > 1e-12f) dp[j] = (g[j][k] - e[j][k] * dot / sq) / nrm;
+                    else dp[j] = g[j][k] / 1e-12f;
+                }
+                if (!(mode & (1 << j))) dp[j] = 0.f;
+            }
+            ga[c] = dp[2] * inv + dp[3] / rs;
+            gb[c] = dp[4] / wd;
+            gc[c] = dp[0];
+            gm[c] = dp[1];
+            am[c] = want_max ? argmax[(size_t)s * H + c] : -1;
+        }
+    }
+    __syncthreads();
+    f32x2 a[POOL_VPL], b[POOL_VPL], mg[POOL_VPL];
+    int ai[POOL_VPL][2];
+#pragma unroll
+    for (int i = 0; i < POOL_VPL; ++i) {
+        const int c = lane + 64 * i;
+        a[i][0] = a[i][1] = b[i][0] = b[i][1] = mg[i][0] = mg[i][1] = 0.f;
+        ai[i][0] = ai[i][1] = -1;
+        if (c < nv) {
+            a[i] = *(const f32x2*)(ga + 2 * c);
+            b[i] = *(const f32x2*)(gb + 2 * c);
+            if (want_max) { mg[i] = *(const f32x2*)(gm + 2 * c); ai[i][0] = am[2 * c]; ai[i][1] = am[2 * c + 1]; }
+        }
+    }
+    for (int t = wave; t < L; t += POOL_WAVES) {
+        const float m = msk[t], wt = m * (float)(t + 1);
+        float* row = dtok + ((size_t)s * L + t) * H;
+#pragma unroll
+        for (int i = 0; i < POOL_VPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nv) {
+                f32x2 r = a[i] * m + b[i] * wt;
+                if (want_cls && t == 0) r += *(const f32x2*)(gc + 2 * c);
+                if (want_max) {
+                    if (ai[i][0] == t) r[0] += mg[i][0];
+                    if (ai[i][1] == t) r[1] += mg[i][1];
+                }
+                *(f32x2*)(row + 2 * c) = r;
+            }
+        }
+    }
+}
+
 // MPNet relative position bias (modeling_mpnet.py:312-348): rel[a,i,j] = table[bucket(j-i)][a]. The bucket of each
 // offset comes from a host-built LUT (qst_rel_bucket_host) so the float32 log matches torch's on the boundaries.
 __global__ void rel_bias_fwd_kernel(const float* table, const int32_t* lut, int A, int L, float* out) {
@@ -859,6 +1154,30 @@ extern "C" int qst_pool_norm_bwd(const float* demb, const float* pooled, const i
     if (L > 512 || H > 1024) return QST_ERR_UNSUPPORTED;
     if (H & 1) return QST_ERR_UNSUPPORTED;
     pool_norm_bwd_kernel<<<nseq, 64 * POOL_WAVES, (size_t)H * sizeof(float), (hipStream_t)stream>>>(demb, pooled, mask, L, H, normalize, dtok);
+    QST_LAUNCH_CHECK();
+    return QST_OK;
+}
+
+extern "C" int qst_pool_fwd(const float* tok, const int64_t* mask, int nseq, int L, int H, int mode, int normalize,
+                            float* emb, float* pooled, int32_t* argmax, void* stream) {
+    if (!tok || !mask || !emb || nseq <= 0 || L <= 0 || H <= 0 || mode <= 0 || mode > QST_POOL_ALL) return QST_ERR_BAD_ARG;
+    if (L > 512 || H > 1024) return QST_ERR_UNSUPPORTED;
+    if (H & 1) return QST_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)POOL_WAVES * H * ((mode & QST_POOL_MAX) ? sizeof(float) + sizeof(int) : sizeof(float));
+    pool_fwd_kernel<<<nseq, 64 * POOL_WAVES, lds, (hipStream_t)stream>>>(tok, mask, L, H, mode, normalize, emb, pooled, argmax);
+    QST_LAUNCH_CHECK();
+    return QST_OK;
+}
+
+extern "C" int qst_pool_bwd(const float* demb, const float* pooled, const int32_t* argmax, const int64_t* mask, int nseq, int L,
+                            int H, int mode, int normalize, float* dtok, void* stream) {
+    if (!demb || !pooled || !mask || !dtok || nseq <= 0 || L <= 0 || H <= 0 || mode <= 0 || mode > QST_POOL_ALL)
+        return QST_ERR_BAD_ARG;
+    if ((mode & QST_POOL_MAX) && !argmax) return QST_ERR_BAD_ARG;
+    if (L > 512 || H > 1024) return QST_ERR_UNSUPPORTED;
+    if (H & 1) return QST_ERR_UNSUPPORTED;
+    pool_bwd_kernel<<<nseq, 64 * POOL_WAVES, (size_t)5 * H * sizeof(float), (hipStream_t)stream>>>(demb, pooled, argmax, mask, L, H,
+                                                                                                     mode, normalize, dtok);
     QST_LAUNCH_CHECK();
     return QST_OK;
 }

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import EncoderConfig, build_layout, hf_param_views
+from .config import EncoderConfig, build_layout, hf_param_views, pooling_mask
 
 
 def _round_up(n: int, m: int) -> int:
@@ -33,9 +33,11 @@ class HipEncoder:
         n = self.lib.qst_arena_elems(self.ccfg)
         if n != self.total:
             raise _lib.QstError(f"arena layout mismatch: python {self.total} vs libqst {n}")
-        h = _lib.vp()
-        _lib.check(self.lib.qst_encoder_create(self.ccfg, h), "qst_encoder_create")
-        self.handle = h
+        self.pool_mode = pooling_mask(cfg.pooling)     # include/qst.h QST_POOL_*: set on every handle this encoder creates
+        self.handle = self._create(self.ccfg, "qst_encoder_create")
+        self.emb_dim = self.lib.qst_encoder_embedding_dim(self.handle)
+        if self.emb_dim != cfg.embedding_dim:
+            raise _lib.QstError(f"embedding width mismatch: python {cfg.embedding_dim} vs libqst {self.emb_dim}")
         self.dropout = None           # (p_hidden, p_attn, seed) once set_dropout() switched it on
         self.dropout_step = 0
         self.drop_state = None
@@ -65,6 +67,17 @@ class HipEncoder:
         self._step_dev: Optional[torch.Tensor] = None    # device-side optimiser step counter (graph-captured steps)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.opt_step = 0
+
+    def _create(self, ccfg, what: str):
+        """A new encoder handle with this encoder's pooling head."""
+        h = _lib.vp()
+        _lib.check(self.lib.qst_encoder_create(ccfg, h), what)
+        if self.pool_mode != pooling_mask("mean"):
+            st = self.lib.qst_encoder_set_pooling(h, self.pool_mode)
+            if st != 0:
+                self.lib.qst_encoder_destroy(h)
+                _lib.check(st, "qst_encoder_set_pooling")
+        return h
 
     def __del__(self):
         try:
@@ -213,8 +226,7 @@ class HipEncoder:
             return self.handle
         if precision in ("fp8", 3):
             if self.handle_mx is None:
-                h = _lib.vp()
-                _lib.check(self.lib.qst_encoder_create(_lib.make_config(self.cfg, 3), h), "qst_encoder_create(fp8)")
+                h = self._create(_lib.make_config(self.cfg, 3), "qst_encoder_create(fp8)")
                 self.handle_mx = h
                 self.shadow_mx = torch.zeros(self.lib.qst_shadow8_bytes(self.ccfg), dtype=torch.uint8, device=self.device)
                 self.shadow_mx_stale = True
@@ -224,8 +236,7 @@ class HipEncoder:
             return self.handle_mx
         if precision in ("f16", "fp16", 4):
             if self.handle_f16 is None:
-                h = _lib.vp()
-                _lib.check(self.lib.qst_encoder_create(_lib.make_config(self.cfg, 4), h), "qst_encoder_create(f16)")
+                h = self._create(_lib.make_config(self.cfg, 4), "qst_encoder_create(f16)")
                 self.handle_f16 = h
                 self.shadow_f16 = torch.zeros(self.lib.qst_shadow_elems(self.ccfg), dtype=torch.float16, device=self.device)
                 self.shadow_f16_stale = True
@@ -235,9 +246,8 @@ class HipEncoder:
             return self.handle_f16
         if precision in ("f16w", 5):
             if self.handle_f16w is None:
-                h = _lib.vp()
                 c5 = _lib.make_config(self.cfg, 5)
-                _lib.check(self.lib.qst_encoder_create(c5, h), "qst_encoder_create(f16w)")
+                h = self._create(c5, "qst_encoder_create(f16w)")
                 self.handle_f16w = h
                 self.shadow_f16w = torch.zeros(self.lib.qst_shadow_elems(c5), dtype=torch.float16, device=self.device)
                 self.shadow_f16w_stale = True
@@ -248,8 +258,7 @@ class HipEncoder:
         if precision not in ("bf16x3", 1):
             raise ValueError(f"unknown precision {precision!r} (bf16 | f16 | f16w | bf16x3 | fp8)")
         if self.handle_x3 is None:
-            h = _lib.vp()
-            _lib.check(self.lib.qst_encoder_create(_lib.make_config(self.cfg, 1), h), "qst_encoder_create(x3)")
+            h = self._create(_lib.make_config(self.cfg, 1), "qst_encoder_create(x3)")
             self.handle_x3 = h
             if self.dropout is not None:
                 _lib.check(self.lib.qst_encoder_set_dropout(h, self.dropout[0], self.dropout[1], self.drop_state.data_ptr()),
@@ -259,7 +268,8 @@ class HipEncoder:
     def forward(self, ids: torch.Tensor, mask: torch.Tensor, type_ids: Optional[torch.Tensor] = None,
                 training: bool = False, want_tokens: bool = False, saved: Optional[torch.Tensor] = None,
                 precision: str = "bf16"):
-        """ids/mask int64 [n, L] on this device, L % 32 == 0. Returns (emb [n,H], tok [n,L,H] or None, saved).
+        """ids/mask int64 [n, L] on this device, L % 32 == 0. Returns (emb [n,D], tok [n,L,H] or None, saved); D =
+        cfg.embedding_dim (H for mean pooling).
         precision="bf16x3" runs the fp32-class parity path, "fp8" the fp8 matrix-core path (MXFP8 weights and
         activations). training=True keeps what the matching backward(precision=...) needs."""
         assert ids.dtype == torch.int64 and mask.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
@@ -285,7 +295,7 @@ class HipEncoder:
             raise _lib.QstError(f"unsupported shape nseq={n} L={L} for this encoder (L % 32 == 0, L <= 512)")
         if saved is None:
             saved = self._arena("_saved_x3" if handle in (self.handle_x3, self.handle_mx) and training else "_saved", nbytes)
-        emb = torch.empty(n, self.cfg.hidden_size, dtype=torch.float32, device=self.device)
+        emb = torch.empty(n, self.emb_dim, dtype=torch.float32, device=self.device)
         tok = torch.empty(n, L, self.cfg.hidden_size, dtype=torch.float32, device=self.device) if want_tokens else None
         _lib.check(self.lib.qst_encoder_forward(
             handle, ids.data_ptr(), mask.data_ptr(), _lib.ptr(type_ids), n, L, self.params.data_ptr(),

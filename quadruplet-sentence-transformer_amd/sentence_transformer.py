@@ -21,6 +21,7 @@ import shutil
 import tempfile
 import zlib
 from collections import OrderedDict
+from dataclasses import replace
 from typing import Callable, Dict, Iterable, List, Optional, Tuple, Type, Union
 
 import numpy as np
@@ -30,6 +31,7 @@ from torch import nn
 from . import _lib
 from .config import ARCH_BERT, ARCH_MPNET, PRESETS, EncoderConfig, hf_param_views
 from .encoder import HipEncoder
+from .models import Normalize, Pooling, Transformer, pooling_from_config
 from .synthetic import synthetic_params
 from .trainer import allreduce_ranges, gradient_buckets, staged_backward, staged_reduce_order, warmup_linear_lr
 
@@ -187,13 +189,14 @@ class SentenceTransformer(nn.Module):
         architecture are available on request only: `allow_random_init=True` (or QST_ALLOW_RANDOM_INIT=1), or an
         explicit `config=`; the `tiny-*` presets are synthetic test architectures and always random-init."""
         super().__init__()
-        if modules is not None:
-            raise NotImplementedError("custom module lists are outside the hot path this build covers")
         self._model_card_name = model_name_or_path
         arena = None
         tok_dir = None
         self._dropout_config = (0.1, 0.1)        # HF defaults; a loaded config.json overrides (fit(dropout="config"))
-        if config is not None:
+        if modules is not None:
+            # models.Transformer -> models.Pooling -> [models.Normalize]: the one chain the library runs
+            cfg, arena, tok_dir, self._dropout_config = _load_module_chain(modules, cache_folder)
+        elif config is not None:
             cfg = config
         elif model_name_or_path is not None and os.path.isdir(str(model_name_or_path)):
             cfg, arena, tok_dir = _load_model_dir(str(model_name_or_path))
@@ -281,7 +284,7 @@ class SentenceTransformer(nn.Module):
         return self
 
     def get_sentence_embedding_dimension(self) -> int:
-        return self.cfg.hidden_size
+        return self.cfg.embedding_dim
 
     def get_max_seq_length(self) -> int:
         return self.max_seq_length
@@ -338,9 +341,13 @@ class SentenceTransformer(nn.Module):
                output_value: str = "sentence_embedding", convert_to_numpy: bool = True,
                convert_to_tensor: bool = False, device: Optional[str] = None, normalize_embeddings: bool = False,
                precision: Optional[str] = None):
-        """precision: None = self.inference_precision; "bf16x3" = embeddings within rtol 1e-3/atol 1e-4 of fp32."""
-        if output_value != "sentence_embedding":
-            raise NotImplementedError("only output_value='sentence_embedding' is on the accelerated path")
+        """precision: None = self.inference_precision; "bf16x3" = embeddings within rtol 1e-3/atol 1e-4 of fp32.
+        output_value="token_embeddings": per sentence the final token states [n_tokens, H], trimmed to its attention mask's
+        length, as ST 2.2.2 returns them (a list; tensors, or numpy arrays with convert_to_numpy)."""
+        if output_value not in ("sentence_embedding", "token_embeddings"):
+            raise NotImplementedError("output_value is 'sentence_embedding' or 'token_embeddings'")
+        if output_value == "token_embeddings":
+            return self._encode_tokens(sentences, batch_size, convert_to_numpy and not convert_to_tensor, precision)
         was_training, was_prec = self.training, self.inference_precision
         if precision is not None:
             self.inference_precision = precision
@@ -362,7 +369,7 @@ class SentenceTransformer(nn.Module):
                     _lib.check(self._enc.lib.qst_normalize_rows(emb.data_ptr(), emb.shape[0], emb.shape[1], emb.data_ptr(),
                                                                 _lib.current_stream_ptr()), "qst_normalize_rows")
                 chunks.append(emb.cpu() if convert_to_numpy else emb)
-        allemb = torch.cat(chunks, 0) if chunks else torch.zeros(0, self.cfg.hidden_size)
+        allemb = torch.cat(chunks, 0) if chunks else torch.zeros(0, self.cfg.embedding_dim)
         inv = np.argsort(order)
         allemb = allemb[torch.as_tensor(inv, device=allemb.device)] if len(inv) else allemb
         if convert_to_numpy:
@@ -372,6 +379,27 @@ class SentenceTransformer(nn.Module):
         self.train(was_training)
         self.inference_precision = was_prec
         return allemb
+
+    def _encode_tokens(self, sentences, batch_size: int, to_numpy: bool, precision: Optional[str]):
+        """encode(output_value="token_embeddings"): the forward's token states (want_tokens), each row trimmed to its mask."""
+        single = isinstance(sentences, str) or not hasattr(sentences, "__len__")
+        if single:
+            sentences = [sentences]
+        prec = precision if precision is not None else self.inference_precision
+        out = []
+        with torch.no_grad(), torch.cuda.device(self._target_device):
+            for start in range(0, len(sentences), batch_size):
+                feats = self.tokenize(list(sentences[start:start + batch_size]))
+                ids = feats["input_ids"].to(self._target_device, torch.int64)
+                mask = feats["attention_mask"].to(self._target_device, torch.int64)
+                types = feats.get("token_type_ids") if self.cfg.type_vocab_size > 0 else None
+                types = types.to(self._target_device, torch.int64) if types is not None else None
+                ids, mask, types, _ = HipEncoder.pad_inputs(ids, mask, types, self.cfg.pad_token_id)
+                _, tok, _ = self._enc.forward(ids, mask, types, training=False, want_tokens=True, precision=prec)
+                for i, n in enumerate(mask.sum(1).tolist()):
+                    t = tok[i, :int(n)]
+                    out.append(t.cpu().numpy() if to_numpy else t)
+        return out[0] if single else out
 
     # ---- fit (SURVEY.md 3.1 / 8a row a8; kwargs = training/main.py:128-148)
     def fit(self, train_objectives: Iterable[Tuple[object, nn.Module]], evaluator=None, epochs: int = 1,
@@ -617,6 +645,9 @@ class SentenceTransformer(nn.Module):
         if (cfg.hidden_size, cfg.num_layers, cfg.vocab_size, cfg.arch) != (self.cfg.hidden_size, self.cfg.num_layers,
                                                                             self.cfg.vocab_size, self.cfg.arch):
             raise ValueError(f"{path}: checkpoint architecture differs from this model")
+        if (cfg.pooling, cfg.normalize) != (self.cfg.pooling, self.cfg.normalize):
+            raise ValueError(f"{path}: checkpoint head (pooling {cfg.pooling!r}, normalize {cfg.normalize}) differs from this "
+                             f"model's (pooling {self.cfg.pooling!r}, normalize {self.cfg.normalize})")
         self._enc.load_arena(arena)
         st = load_file(state_file)
         st["opt_step"] = torch.tensor([int(meta["opt_step"])], dtype=torch.int64)
@@ -647,10 +678,12 @@ class SentenceTransformer(nn.Module):
         modules = [{"idx": 0, "name": "0", "path": "", "type": "sentence_transformers.models.Transformer"},
                    {"idx": 1, "name": "1", "path": "1_Pooling", "type": "sentence_transformers.models.Pooling"}]
         os.makedirs(os.path.join(path, "1_Pooling"), exist_ok=True)
-        json.dump({"word_embedding_dimension": cfg.hidden_size, "pooling_mode_cls_token": False,
-                   "pooling_mode_mean_tokens": True, "pooling_mode_max_tokens": False,
-                   "pooling_mode_mean_sqrt_len_tokens": False},
-                  open(os.path.join(path, "1_Pooling", "config.json"), "w"), indent=2)
+        pool = {"word_embedding_dimension": cfg.hidden_size, "pooling_mode_cls_token": False,
+                "pooling_mode_mean_tokens": True, "pooling_mode_max_tokens": False,
+                "pooling_mode_mean_sqrt_len_tokens": False}
+        if cfg.pooling != "mean":                          # (the mean head's file stays what it always was)
+            pool = Pooling(cfg.hidden_size, pooling_mode=cfg.pooling).get_config_dict()
+        json.dump(pool, open(os.path.join(path, "1_Pooling", "config.json"), "w"), indent=2)
         if cfg.normalize:
             modules.append({"idx": 2, "name": "2", "path": "2_Normalize", "type": "sentence_transformers.models.Normalize"})
             os.makedirs(os.path.join(path, "2_Normalize"), exist_ok=True)
@@ -716,6 +749,32 @@ def _find_cached_model(name: str, cache_folder: Optional[str] = None) -> Optiona
     return None
 
 
+def _load_module_chain(modules, cache_folder: Optional[str] = None):
+    """SentenceTransformer(modules=[models.Transformer, models.Pooling, models.Normalize (optional)]): (cfg, arena,
+    tokenizer dir, dropout config) of the Transformer's checkpoint with the head the Pooling / Normalize descriptors name.
+    Any other module list is refused."""
+    mods = list(modules.values()) if isinstance(modules, (dict, OrderedDict)) else list(modules)
+    kinds = [type(m) for m in mods]
+    if kinds not in ([Transformer, Pooling], [Transformer, Pooling, Normalize]):
+        raise NotImplementedError("custom module lists are outside the hot path this build covers: only "
+                                  "[models.Transformer, models.Pooling] and [..., models.Normalize] are accepted, got "
+                                  f"{[k.__name__ for k in kinds]}")
+    tr, pool = mods[0], mods[1]
+    path = str(tr.model_name_or_path)
+    if not os.path.isdir(path):
+        found = _find_cached_model(path, tr.cache_dir or cache_folder)
+        if found is None:
+            raise FileNotFoundError(f"models.Transformer({path!r}): no checkpoint on this machine (no network access)")
+        path = found
+    cfg, arena, tok_dir = _load_model_dir(path)
+    if pool.word_embedding_dimension != cfg.hidden_size:
+        raise NotImplementedError(f"models.Pooling({pool.word_embedding_dimension}, ...): word_embedding_dimension differs "
+                                  f"from the checkpoint's hidden_size {cfg.hidden_size}")
+    max_seq = cfg.max_seq_length if tr.max_seq_length is None else min(512, int(tr.max_seq_length))
+    cfg = replace(cfg, pooling=pool.pooling, normalize=len(mods) == 3, max_seq_length=max_seq)
+    return cfg, arena, tok_dir, _dropout_from_config(path)
+
+
 def _dropout_from_config(path: str):
     """(hidden_dropout_prob, attention_probs_dropout_prob) of a model directory's config.json, HF defaults 0.1 / 0.1."""
     try:
@@ -735,6 +794,7 @@ def _load_model_dir(path: str):
     if mt not in ("bert", "mpnet"):
         raise NotImplementedError(f"model_type '{mt}' is not on the accelerated path (bert, mpnet)")
     normalize, max_seq = False, min(512, int(hf.get("max_position_embeddings", 512)))
+    pooling = "mean"
     mj = os.path.join(path, "modules.json")
     if os.path.exists(mj):
         mods = json.load(open(mj))
@@ -743,15 +803,11 @@ def _load_model_dir(path: str):
             kind = m.get("type", "").rsplit(".", 1)[-1]
             if kind not in ("Transformer", "Pooling", "Normalize"):
                 raise NotImplementedError(f"{path}: module '{m.get('type')}' is not on the accelerated path "
-                                          "(Transformer -> Pooling(mean) -> [Normalize])")
+                                          "(Transformer -> Pooling -> [Normalize])")
             if kind == "Pooling":
                 pc = os.path.join(path, m.get("path", "1_Pooling"), "config.json")
                 if os.path.exists(pc):
-                    pool = json.load(open(pc))
-                    on = sorted(k for k, v in pool.items() if k.startswith("pooling_mode_") and v)
-                    if on != ["pooling_mode_mean_tokens"]:
-                        raise NotImplementedError(f"{path}: pooling {on} -- only mean-token pooling is implemented "
-                                                  "(pool_norm_fwd/bwd); this checkpoint would be pooled wrongly")
+                    pooling = pooling_from_config(json.load(open(pc)), int(hf["hidden_size"]), path)
     sb = os.path.join(path, "sentence_bert_config.json")
     if os.path.exists(sb):
         max_seq = int(json.load(open(sb)).get("max_seq_length", max_seq))
@@ -762,7 +818,7 @@ def _load_model_dir(path: str):
                         type_vocab_size=0 if arch == ARCH_MPNET else hf.get("type_vocab_size", 2),
                         layer_norm_eps=hf.get("layer_norm_eps", 1e-12), normalize=normalize, max_seq_length=max_seq,
                         rel_buckets=hf.get("relative_attention_num_buckets", 32),
-                        pad_token_id=hf.get("pad_token_id", 1 if arch == ARCH_MPNET else 0))
+                        pad_token_id=hf.get("pad_token_id", 1 if arch == ARCH_MPNET else 0), pooling=pooling)
     st_path = os.path.join(path, "model.safetensors")
     if os.path.exists(st_path):
         from safetensors.torch import load_file
