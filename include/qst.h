@@ -55,7 +55,10 @@ typedef enum {
     QST_ERR_NO_FORWARD = -7    /* backward over an arena that no training forward of this precision and shape has filled */
 } qst_status;
 
-enum { QST_ARCH_BERT = 0, QST_ARCH_MPNET = 1 };
+/* QST_ARCH_ROBERTA (RoBERTa / XLM-R): BERT's post-LN layer stack and parameter layout, no relative-attention bias,
+ * position ids from the padding as MPNet's (pad_token_id + cumsum(ids != pad_token_id), pad 1), a token-type table of
+ * type_vocab_size rows (1 in real checkpoints; the ids are all 0). */
+enum { QST_ARCH_BERT = 0, QST_ARCH_MPNET = 1, QST_ARCH_ROBERTA = 2 };
 enum { QST_PREC_BF16 = 0, QST_PREC_BF16X3 = 1, QST_PREC_FP8 = 3, QST_PREC_F16 = 4, QST_PREC_F16W = 5 };   /* 2 was an fp8-weights-only mode (removed) */
 enum { QST_REDUCE_NONE = 0, QST_REDUCE_SUM = 1, QST_REDUCE_MEAN = 2 };
 
@@ -69,12 +72,12 @@ typedef struct {
     int32_t num_heads;         /* H / num_heads must be 32 or 64                       */
     int32_t intermediate_size; /* I; multiple of 64                                    */
     int32_t max_position;
-    int32_t type_vocab_size;   /* 0 for MPNet                                          */
+    int32_t type_vocab_size;   /* 0 for MPNet, 1 for RoBERTa                           */
     float   layer_norm_eps;
     int32_t normalize;         /* ST Normalize module present                          */
     int32_t rel_buckets;       /* MPNet relative_attention_num_buckets (32)            */
     int32_t rel_max_distance;  /* MPNet (128)                                          */
-    int32_t pad_token_id;      /* MPNet position ids (1)                               */
+    int32_t pad_token_id;      /* MPNet / RoBERTa position ids (1)                     */
     int32_t precision;         /* QST_PREC_*                                           */
 } qst_config;
 
@@ -296,6 +299,18 @@ int qst_score_matrix(const float* queries, const float* corpus, int nq, int nc, 
 /* torch.nn.functional.normalize(x, p=2, dim=1, eps=1e-12) over the rows of x f32 [n, dim] (contiguous): what
  * SentenceTransformer.encode(normalize_embeddings=True) applies. out may alias x. */
 int qst_normalize_rows(const float* x, int n, int dim, float* out, void* stream);
+
+/* The classification head of a cross-encoder (version 102): what transformers' BertForSequenceClassification (pooler +
+ * classifier) and RobertaForSequenceClassification (classifier.dense + out_proj) put on the encoder's first token, and
+ * sentence-transformers 2.2.2 CrossEncoder.predict's activation, in one launch, all in fp32:
+ *   h = tanh(W1 x + b1), z = W2 h + b2, out = act(z), then softmax over the C labels when softmax != 0 and C > 1.
+ *   x   : f32 [n, H] rows with stride ldx >= H (qst_encoder_forward's out_emb with QST_POOL_CLS and normalize = 0)
+ *   w1  : f32 [H, H] (16-byte aligned), b1 f32 [H]; w2 f32 [C, H], b2 f32 [C]   (torch.nn.Linear layout: [out, in])
+ *   act : QST_HEAD_ACT_NONE (identity) or QST_HEAD_ACT_SIGMOID;  out: f32 [n, C]
+ * H <= 1024 and a multiple of 4, 1 <= C <= 8; anything else is refused (QST_ERR_BAD_ARG / QST_ERR_UNSUPPORTED). */
+enum { QST_HEAD_ACT_NONE = 0, QST_HEAD_ACT_SIGMOID = 1 };
+int qst_cls_head_fwd(const float* x, int64_t ldx, int n, int H, const float* w1, const float* b1, const float* w2,
+                     const float* b2, int C, int act, int softmax, float* out, void* stream);
 
 
 /* The same with a ceiling: corpus rows scoring above max_score do not take part. This is the reference's negative

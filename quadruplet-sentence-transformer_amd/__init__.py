@@ -7,4 +7,12 @@ csrc/ (libqst.so) -- there is no CPU or torch fallback.
 """
 from .config import EncoderConfig, PRESETS, build_layout  # noqa: F401
 
-__all__ = ["EncoderConfig", "PRESETS", "build_layout"]
+__all__ = ["EncoderConfig", "PRESETS", "build_layout", "CrossEncoder"]
+
+
+def __getattr__(name):
+    # CrossEncoder pulls in torch and the encoder front end: imported on first use, not with the package
+    if name == "CrossEncoder":
+        from .cross_encoder import CrossEncoder
+        return CrossEncoder
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -155,6 +155,7 @@ SIGNATURES = {
     "qst_dropout_multipliers": (C.c_int, [C.POINTER(QstDrop), C.c_int, C.c_int64, vp, vp]),
     "qst_abi_sizeof": (C.c_int64, [C.c_int]),
     "qst_normalize_rows": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "qst_cls_head_fwd": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "qst_dropout_init": (C.c_int, [vp, C.c_uint64, vp]),
     "qst_dropout_advance": (C.c_int, [vp, vp]),
     "qst_encoder_set_dropout": (C.c_int, [vp, C.c_float, C.c_float, vp]),

@@ -21,6 +21,9 @@ ARENA_ALIGN = 256  # elements
 
 ARCH_BERT = 0
 ARCH_MPNET = 1
+# RoBERTa / XLM-R (include/qst.h QST_ARCH_ROBERTA): BERT's layer stack and parameter names, MPNet's position ids (from the
+# padding, pad 1), a one-row token-type table
+ARCH_ROBERTA = 2
 
 # sentence-transformers 2.2.2 models.Pooling modes, in the fixed order in which their [n, H] blocks are concatenated
 # (whatever order a caller names them in); bit i of the C-ABI's mode mask (include/qst.h QST_POOL_*) is POOLING_MODES[i]
@@ -100,6 +103,14 @@ PRESETS: Dict[str, EncoderConfig] = {
     # (GEMM + LayerNorm fused, 8-range grouped wgrad, single-workgroup attention backward: M >= 16384 token rows) while
     # staying cheap for the HF reference on the CPU (tests/golden/encoder_golden.npz: minilm2l_fused)
     "minilm-2l": EncoderConfig(num_layers=2, vocab_size=4096),
+    # RoBERTa: the tiny parity fixture (positions 2 .. 65 for 64 tokens) and stsb-roberta-large's widths (H=1024, 16 heads,
+    # I=4096, P=514, one type row, eps 1e-5) on two layers and a 4,096-word vocabulary
+    "tiny-roberta": EncoderConfig(
+        arch=ARCH_ROBERTA, vocab_size=128, hidden_size=64, num_layers=2, num_heads=2, intermediate_size=256,
+        max_position=66, type_vocab_size=1, layer_norm_eps=1e-5, normalize=False, max_seq_length=64, pad_token_id=1),
+    "roberta-large-2l": EncoderConfig(
+        arch=ARCH_ROBERTA, vocab_size=4096, hidden_size=1024, num_layers=2, num_heads=16, intermediate_size=4096,
+        max_position=514, type_vocab_size=1, layer_norm_eps=1e-5, normalize=False, max_seq_length=512, pad_token_id=1),
 }
 
 
@@ -178,7 +189,7 @@ def hf_param_views(cfg: EncoderConfig) -> List[Tuple[str, str, int, Tuple[int, .
             ("embeddings.LayerNorm.bias", "emb_ln_b", 0, (H,))]
     for l in range(cfg.num_layers):
         s = f"layer.{l}."
-        if cfg.arch == ARCH_BERT:
+        if cfg.arch in (ARCH_BERT, ARCH_ROBERTA):          # RoBERTa keeps BERT's module names
             p = f"encoder.layer.{l}."
             qkv = [p + "attention.self.query", p + "attention.self.key", p + "attention.self.value"]
             o, ln1 = p + "attention.output.dense", p + "attention.output.LayerNorm"

@@ -15,7 +15,7 @@
 static thread_local int g_last_hip_error = 0;
 extern "C" int qst_set_hip_error(int code) { g_last_hip_error = code; return code; }
 extern "C" int qst_last_hip_error(void) { return g_last_hip_error; }
-extern "C" int qst_version(void) { return 101; }
+extern "C" int qst_version(void) { return 102; }
 
 extern "C" const char* qst_strerror(int s) {
     switch (s) {
@@ -55,7 +55,7 @@ struct Layout {
 
 bool cfg_ok(const qst_config* c) {
     if (!c) return false;
-    if (c->arch != QST_ARCH_BERT && c->arch != QST_ARCH_MPNET) return false;
+    if (c->arch != QST_ARCH_BERT && c->arch != QST_ARCH_MPNET && c->arch != QST_ARCH_ROBERTA) return false;
     if (c->hidden_size <= 0 || c->num_layers <= 0 || c->num_heads <= 0 || c->intermediate_size <= 0) return false;
     if (c->vocab_size <= 0 || c->max_position <= 0 || c->type_vocab_size < 0) return false;
     return true;
@@ -434,7 +434,8 @@ int shape_ok(const qst_encoder* e, int nseq, int L) {
     if (L % 32 != 0 || L > 512) return QST_ERR_UNSUPPORTED;
     if ((int64_t)nseq * L * e->cfg.intermediate_size * 2 >= ((int64_t)1 << 32)) return QST_ERR_UNSUPPORTED;  // 32-bit buffer offsets
     if (e->cfg.arch == QST_ARCH_BERT && L > e->cfg.max_position) return QST_ERR_UNSUPPORTED;
-    if (e->cfg.arch == QST_ARCH_MPNET && L + e->cfg.pad_token_id + 1 > e->cfg.max_position) return QST_ERR_UNSUPPORTED;
+    // MPNet and RoBERTa count positions from pad_token_id + 1
+    if (e->cfg.arch != QST_ARCH_BERT && L + e->cfg.pad_token_id + 1 > e->cfg.max_position) return QST_ERR_UNSUPPORTED;
     return QST_OK;
 }
 

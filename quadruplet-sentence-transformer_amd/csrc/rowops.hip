@@ -369,8 +369,9 @@ __global__ void position_ids_kernel(const int64_t* ids, int nseq, int L, int arc
     if (s >= nseq) return;
     if (arch == QST_ARCH_BERT) {
         for (int t = 0; t < L; ++t) pos[s * L + t] = t;
-    } else {
-        int cum = 0;                                   // modeling_mpnet.py:873-881
+    } else if (arch == QST_ARCH_MPNET || arch == QST_ARCH_ROBERTA) {
+        // modeling_mpnet.py:873-881, modeling_roberta.py create_position_ids_from_input_ids: the same rule
+        int cum = 0;
         for (int t = 0; t < L; ++t) {
             const int m = ids[(size_t)s * L + t] != pad_id;
             cum += m;

@@ -29,7 +29,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .config import ARCH_BERT, ARCH_MPNET, PRESETS, EncoderConfig, hf_param_views
+from .config import ARCH_BERT, ARCH_MPNET, ARCH_ROBERTA, PRESETS, EncoderConfig, hf_param_views
 from .encoder import HipEncoder
 from .models import Normalize, Pooling, Transformer, pooling_from_config
 from .synthetic import synthetic_params
@@ -66,7 +66,7 @@ class SyntheticTokenizer:
 
     def __init__(self, cfg: EncoderConfig):
         self.cfg = cfg
-        if cfg.arch == ARCH_MPNET:
+        if cfg.arch in (ARCH_MPNET, ARCH_ROBERTA):          # <s> = 0, </s> = 2, <pad> = 1
             self.cls_id, self.sep_id, self.pad_id = 0, 2, 1
         else:
             self.cls_id, self.sep_id, self.pad_id = 101 % cfg.vocab_size, 102 % cfg.vocab_size, 0
@@ -665,7 +665,7 @@ class SentenceTransformer(nn.Module):
         from safetensors.torch import save_file
         tensors = OrderedDict((k, v.detach().cpu().contiguous().clone()) for k, v in self._enc.named_views().items())
         save_file(tensors, os.path.join(path, "model.safetensors"))
-        hf = {"model_type": "bert" if cfg.arch == ARCH_BERT else "mpnet", "vocab_size": cfg.vocab_size,
+        hf = {"model_type": _MODEL_TYPES[cfg.arch], "vocab_size": cfg.vocab_size,
               "hidden_size": cfg.hidden_size, "num_hidden_layers": cfg.num_layers,
               "num_attention_heads": cfg.num_heads, "intermediate_size": cfg.intermediate_size,
               "max_position_embeddings": cfg.max_position, "type_vocab_size": cfg.type_vocab_size,
@@ -784,15 +784,27 @@ def _dropout_from_config(path: str):
     return (float(hf.get("hidden_dropout_prob", 0.1)), float(hf.get("attention_probs_dropout_prob", 0.1)))
 
 
+# config.json model_type of each architecture (save()), and the model_types each architecture loads from
+_MODEL_TYPES = {ARCH_BERT: "bert", ARCH_MPNET: "mpnet", ARCH_ROBERTA: "roberta"}
+_ARCH_OF_MODEL_TYPE = {"bert": ARCH_BERT, "mpnet": ARCH_MPNET, "roberta": ARCH_ROBERTA, "xlm-roberta": ARCH_ROBERTA}
+
+
 def _load_model_dir(path: str):
     """Read an ST/HF model directory (as written by save() above or by sentence-transformers)."""
+    cfg, arena, path, _ = _load_model_dir_sd(path)
+    return cfg, arena, path
+
+
+def _load_model_dir_sd(path: str):
+    """_load_model_dir and the checkpoint's whole state dict (model prefixes bert. / mpnet. / roberta. stripped), for the
+    tensors outside the encoder (a cross-encoder's classification head)."""
     cfg_path = os.path.join(path, "config.json")
     if not os.path.exists(cfg_path):
         raise FileNotFoundError(f"{path} has no config.json")
     hf = json.load(open(cfg_path))
     mt = hf.get("model_type", "bert")
-    if mt not in ("bert", "mpnet"):
-        raise NotImplementedError(f"model_type '{mt}' is not on the accelerated path (bert, mpnet)")
+    if mt not in _ARCH_OF_MODEL_TYPE:
+        raise NotImplementedError(f"model_type '{mt}' is not on the accelerated path ({', '.join(_ARCH_OF_MODEL_TYPE)})")
     normalize, max_seq = False, min(512, int(hf.get("max_position_embeddings", 512)))
     pooling = "mean"
     mj = os.path.join(path, "modules.json")
@@ -811,14 +823,19 @@ def _load_model_dir(path: str):
     sb = os.path.join(path, "sentence_bert_config.json")
     if os.path.exists(sb):
         max_seq = int(json.load(open(sb)).get("max_seq_length", max_seq))
-    arch = ARCH_BERT if mt == "bert" else ARCH_MPNET
+    arch = _ARCH_OF_MODEL_TYPE[mt]
+    roberta = arch == ARCH_ROBERTA
+    # RoBERTa: its position table starts at pad_token_id + 1 (max_position 514 = 512 tokens), one token-type row, and
+    # layer_norm_eps as config.json states it (1e-5 in every released checkpoint)
+    if roberta and "sentence_bert_config.json" not in os.listdir(path):
+        max_seq = min(max_seq, int(hf["max_position_embeddings"]) - int(hf.get("pad_token_id", 1)) - 1)
     cfg = EncoderConfig(arch=arch, vocab_size=hf["vocab_size"], hidden_size=hf["hidden_size"],
                         num_layers=hf["num_hidden_layers"], num_heads=hf["num_attention_heads"],
                         intermediate_size=hf["intermediate_size"], max_position=hf["max_position_embeddings"],
-                        type_vocab_size=0 if arch == ARCH_MPNET else hf.get("type_vocab_size", 2),
-                        layer_norm_eps=hf.get("layer_norm_eps", 1e-12), normalize=normalize, max_seq_length=max_seq,
-                        rel_buckets=hf.get("relative_attention_num_buckets", 32),
-                        pad_token_id=hf.get("pad_token_id", 1 if arch == ARCH_MPNET else 0), pooling=pooling)
+                        type_vocab_size=0 if arch == ARCH_MPNET else hf.get("type_vocab_size", 1 if roberta else 2),
+                        layer_norm_eps=hf.get("layer_norm_eps", 1e-5 if roberta else 1e-12), normalize=normalize,
+                        max_seq_length=max_seq, rel_buckets=hf.get("relative_attention_num_buckets", 32),
+                        pad_token_id=hf.get("pad_token_id", 0 if arch == ARCH_BERT else 1), pooling=pooling)
     st_path = os.path.join(path, "model.safetensors")
     if os.path.exists(st_path):
         from safetensors.torch import load_file
@@ -827,8 +844,8 @@ def _load_model_dir(path: str):
         sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
     else:
         raise FileNotFoundError(f"{path} has neither model.safetensors nor pytorch_model.bin")
-    sd = {k[len("bert."):] if k.startswith("bert.") else (k[len("mpnet."):] if k.startswith("mpnet.") else k): v
-          for k, v in sd.items()}
+    prefixes = ("bert.", "mpnet.", "roberta.")
+    sd = {next((k[len(p):] for p in prefixes if k.startswith(p)), k): v for k, v in sd.items()}
     from .config import build_layout
     segs, total = build_layout(cfg)
     so = {s.name: s for s in segs}
@@ -843,4 +860,4 @@ def _load_model_dir(path: str):
         arena[s.offset + off:s.offset + off + n] = sd[name].to(torch.float32).numpy().reshape(-1)
     if missing:
         raise KeyError(f"{path}: checkpoint lacks {len(missing)} tensors, e.g. {missing[:3]}")
-    return cfg, arena, path
+    return cfg, arena, path, sd
