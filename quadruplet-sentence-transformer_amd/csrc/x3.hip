@@ -673,6 +673,7 @@ static int x3_share(int nkt, int tiles, int target) {
 extern "C" int qst_gemm_nt_x3(const QstGemmArgs* a, int epi, void* stream) {
     if (!a || !a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0) return QST_ERR_BAD_ARG;
     if (a->K % XBK != 0 || a->lda % 4 != 0 || a->ldb % 4 != 0 || a->N % 4 != 0 || a->ldc % 4 != 0) return QST_ERR_UNSUPPORTED;
+    if (epi == 1 && a->resid && a->ldr % 4 != 0) return QST_ERR_UNSUPPORTED;     // the residual is read as 16-byte f32x4 rows
     const int tiles = ((a->M + 127) / 128) * ((a->N + 127) / 128);
     const int grid = (((a->M + 127) / 128 + 7) / 8 * 8) * ((a->N + 127) / 128);      // A panels padded to the eight XCDs
     hipStream_t st = (hipStream_t)stream;

@@ -67,8 +67,26 @@ def bfr(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
 
+def opr(dt, t):
+    """t rounded to the 16-bit operand type dt and back"""
+    return t.to(dt).to(torch.float32)
+
+
+OPDT = {"bf16": torch.bfloat16, "f16": torch.float16}
+
+
 @pytest.mark.parametrize("M,H", [(37, 64), (300, 384), (129, 768)])
 def test_row_kernels_apply_the_mask(lib, M, H):
+    row_kernels_apply_the_mask(lib, "bf16", M, H)
+
+
+@pytest.mark.parametrize("M,H", [(37, 64), (300, 384), (129, 768)])
+def test_row_kernels_apply_the_mask_f16(lib, M, H):
+    row_kernels_apply_the_mask(lib, "f16", M, H)
+
+
+def row_kernels_apply_the_mask(lib, op, M, H):
+    dt = OPDT[op]
     g = torch.Generator().manual_seed(M + H)
     seed, step, p = 99, 2, 0.2
     st = make_state(lib, seed, step)
@@ -80,23 +98,23 @@ def test_row_kernels_apply_the_mask(lib, M, H):
     gamma = (1 + 0.1 * torch.randn(H, generator=g)).cuda(); beta = (0.1 * torch.randn(H, generator=g)).cuda()
     outs = []
     for d in (None, drop(st, D.SITE_EMBED, p)):
-        y = torch.empty(M, H, device="cuda"); yb = torch.empty(M, H, dtype=torch.bfloat16, device="cuda")
-        xh = torch.empty(M, H, dtype=torch.bfloat16, device="cuda"); rs = torch.empty(M, device="cuda")
-        _lib.check(lib.qst_embed_ln_fwd_drop(ids.data_ptr(), None, pos.data_ptr(), word.data_ptr(), pemb.data_ptr(), None,
+        y = torch.empty(M, H, device="cuda"); yb = torch.empty(M, H, dtype=dt, device="cuda")
+        xh = torch.empty(M, H, dtype=dt, device="cuda"); rs = torch.empty(M, device="cuda")
+        _lib.check(_lib.kfn(lib, "qst_embed_ln_fwd_drop", op)(ids.data_ptr(), None, pos.data_ptr(), word.data_ptr(), pemb.data_ptr(), None,
                                              gamma.data_ptr(), beta.data_ptr(), 1e-12, M, H, y.data_ptr(), yb.data_ptr(),
                                              xh.data_ptr(), rs.data_ptr(), d, stream()))
         outs.append((y, yb, xh, rs))
     (y0, yb0, xh0, rs0), (y1, yb1, xh1, rs1) = outs
-    assert torch.equal(y1, y0 * mk) and torch.equal(yb1, (y0 * mk).to(torch.bfloat16))
+    assert torch.equal(y1, y0 * mk) and torch.equal(yb1, (y0 * mk).to(dt))
     assert torch.equal(xh0, xh1) and torch.equal(rs0, rs1)                     # the saved normalised row is the undropped one
     # LayerNorm backward: mask on the incoming gradient (a dropout after the LayerNorm) / on the bf16 result only
     dy = torch.randn(M, H, generator=g).cuda()
     res = []
     for dy_in, din, dout in ((dy, None, None), (dy * mk, None, None), (dy, drop(st, D.SITE_EMBED, p), None),
                              (dy, None, drop(st, D.SITE_EMBED, p))):
-        ds = torch.empty(M, H, device="cuda"); dsb = torch.empty(M, H, dtype=torch.bfloat16, device="cuda")
+        ds = torch.empty(M, H, device="cuda"); dsb = torch.empty(M, H, dtype=dt, device="cuda")
         dg = torch.zeros(H, device="cuda"); db = torch.zeros(H, device="cuda")
-        _lib.check(lib.qst_ln_bwd_drop(dy_in.data_ptr(), xh0.data_ptr(), rs0.data_ptr(), gamma.data_ptr(), M, H, ds.data_ptr(),
+        _lib.check(_lib.kfn(lib, "qst_ln_bwd_drop", op)(dy_in.data_ptr(), xh0.data_ptr(), rs0.data_ptr(), gamma.data_ptr(), M, H, ds.data_ptr(),
                                        dsb.data_ptr(), dg.data_ptr(), db.data_ptr(), None, din, dout, stream()))
         torch.cuda.synchronize()
         res.append((ds, dsb, dg, db))
@@ -105,7 +123,7 @@ def test_row_kernels_apply_the_mask(lib, M, H):
         assert torch.equal(a, b)
     for a, b in zip(premasked[2:], masked_in[2:]):                                 # float atomics
         torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-5 * max(1.0, a.abs().max().item()))
-    assert torch.equal(masked_out[0], plain[0]) and torch.equal(masked_out[1], (plain[0] * mk).to(torch.bfloat16))
+    assert torch.equal(masked_out[0], plain[0]) and torch.equal(masked_out[1], (plain[0] * mk).to(dt))
 
 
 @pytest.mark.parametrize("M,K,N", [(300, 384, 384), (1000, 1536, 384), (700, 768, 768), (1300, 3072, 768), (33100, 128, 768)])
@@ -184,42 +202,54 @@ def test_attention_with_dropped_probabilities(lib, n, L, A, d, use_rel):
     """Forward and backward on every attention code path (single-workgroup backward: L <= 128, d = 32; dQ + dK/dV kernels
     otherwise; with and without the relative-position bias) against torch autograd with the same mask
     -- and the two backward paths against each other where both apply."""
+    attention_with_dropped_probabilities(lib, "bf16", n, L, A, d, use_rel)
+
+
+@pytest.mark.parametrize("n,L,A,d,use_rel", [(2, 32, 2, 32, False), (3, 128, 12, 32, False), (2, 160, 2, 64, True),
+                                              (2, 64, 2, 32, True), (2, 96, 2, 64, True)])
+def test_attention_with_dropped_probabilities_f16(lib, n, L, A, d, use_rel):
+    """The same on the f16 twins (qst_attention_fwd_ex_f16 / qst_attention_bwd_ex_f16)."""
+    attention_with_dropped_probabilities(lib, "f16", n, L, A, d, use_rel)
+
+
+def attention_with_dropped_probabilities(lib, op, n, L, A, d, use_rel):
+    dt = OPDT[op]
     H = A * d
     g = torch.Generator().manual_seed(n * L + A + d)
     seed, step, p, site = 31337, 4, 0.1, D.site_probs(1)
     st = make_state(lib, seed, step)
     pm = torch.from_numpy(D.multipliers8(seed, step, site, n * A * L * L, p).reshape(n, A, L, L))
-    qkv = bfr(torch.randn(n * L, 3 * H, generator=g))
+    qkv = opr(dt, torch.randn(n * L, 3 * H, generator=g))
     lens = torch.randint(max(1, L // 8), L + 1, (n,), generator=g); lens[0] = L
     mask = (torch.arange(L)[None, :] < lens[:, None]).long()
     relpos = (0.5 * torch.randn(A, 2 * L, generator=g)) if use_rel else None
     ridx = (torch.arange(L)[None, :] - torch.arange(L)[:, None]) + L
-    dctx = bfr(torch.randn(n * L, H, generator=g))
+    dctx = opr(dt, torch.randn(n * L, H, generator=g))
     qr = qkv.clone().requires_grad_(True)
     relr = relpos.clone().requires_grad_(True) if use_rel else None
     ref = attn_ref(qr, mask, relr[:, ridx] if use_rel else None, n, L, A, d, pm)
     (ref * dctx).sum().backward()
 
-    qd = qkv.to(torch.bfloat16).cuda(); md = mask.cuda(); reld = relpos.cuda() if use_rel else None
-    ctx = torch.empty(n * L, H, dtype=torch.bfloat16, device="cuda"); lse = torch.empty(n, A, L, device="cuda")
+    qd = qkv.to(dt).cuda(); md = mask.cuda(); reld = relpos.cuda() if use_rel else None
+    ctx = torch.empty(n * L, H, dtype=dt, device="cuda"); lse = torch.empty(n, A, L, device="cuda")
     q = _lib.QstAttnDesc()
     q.qkv, q.mask, q.rel_pos, q.nseq, q.L, q.A, q.d = qd.data_ptr(), md.data_ptr(), _lib.ptr(reld), n, L, A, d
     q.ctx, q.lse, q.drop = ctx.data_ptr(), lse.data_ptr(), drop(st, site, p)
-    _lib.check(lib.qst_attention_fwd_ex(q, stream()))
+    _lib.check(_lib.kfn(lib, "qst_attention_fwd_ex", op)(q, stream()))
     torch.testing.assert_close(ctx.float().cpu(), ref.detach(), rtol=2e-2, atol=2e-2)
     # lse is the log-sum-exp of the UNDROPPED scores: same as a forward without dropout
     q0 = _lib.QstAttnDesc.from_buffer_copy(q)
     q0.drop = _lib.QstDrop()
     ctx0 = torch.empty_like(ctx); lse0 = torch.empty_like(lse)
     q0.ctx, q0.lse = ctx0.data_ptr(), lse0.data_ptr()
-    _lib.check(lib.qst_attention_fwd_ex(q0, stream()))
+    _lib.check(_lib.kfn(lib, "qst_attention_fwd_ex", op)(q0, stream()))
     assert torch.equal(lse, lse0) and not torch.equal(ctx, ctx0)
 
-    dq = torch.empty(n * L * 3 * H, dtype=torch.bfloat16, device="cuda")
+    dq = torch.empty(n * L * 3 * H, dtype=dt, device="cuda")
     drel = torch.zeros(A, 2 * L, device="cuda") if use_rel else None
-    dcd = dctx.to(torch.bfloat16).cuda(); delta = torch.empty(n, A, L, device="cuda")
+    dcd = dctx.to(dt).cuda(); delta = torch.empty(n, A, L, device="cuda")
     q.dctx, q.dqkv, q.drel, q.delta_scratch = dcd.data_ptr(), dq.data_ptr(), _lib.ptr(drel), delta.data_ptr()
-    _lib.check(lib.qst_attention_bwd_ex(q, stream()))
+    _lib.check(_lib.kfn(lib, "qst_attention_bwd_ex", op)(q, stream()))
     gref = qr.grad
     got = dq.view(n * L, 3 * H).float().cpu()
     assert (got - gref).abs().max().item() <= 3e-2 * max(1.0, gref.abs().max().item())
@@ -231,7 +261,7 @@ def test_attention_with_dropped_probabilities(lib, n, L, A, d, use_rel):
         drel2 = torch.zeros(A, 2 * L, device="cuda") if use_rel else None
         q.dqkv, q.drel = dq2.data_ptr(), _lib.ptr(drel2)
         q.force_split = 1
-        _lib.check(lib.qst_attention_bwd_ex(q, stream()))
+        _lib.check(_lib.kfn(lib, "qst_attention_bwd_ex", op)(q, stream()))
         torch.cuda.synchronize()
         torch.testing.assert_close(dq.float(), dq2.float(), rtol=2e-2, atol=2e-2 * max(1.0, gref.abs().max().item()))
 

@@ -1,4 +1,6 @@
-"""GPU parity of every HIP kernel (through the C-ABI) against the CPU oracle / plain torch fp32.
+"""GPU parity of HIP kernels (through the C-ABI) against the CPU oracle / plain torch fp32. The row kernels are checked in
+test_gpu_row_kernels.py, the parity-precision helpers in test_gpu_parity_kernels.py; test_kernel_coverage_host.py checks that
+every entry point of include/qst_kernels.h is called by name from some GPU test.
 
 Tolerances: kernels that round operands to bf16 are compared with a reference fed the SAME
 bf16-rounded operands (fp32 accumulate), so only accumulation order differs: rtol 2e-3 on
@@ -219,7 +221,8 @@ def test_gemm_tn_group_matches_individual(lib, op, tn_mode, M):
 
 
 # ------------------------------------------------------------------ LayerNorm
-@pytest.mark.parametrize("M,H", [(37, 64), (128, 128), (300, 384), (129, 768), (5, 1024)])
+@pytest.mark.parametrize("M,H", [(37, 64), (128, 128), (300, 384), (129, 768), (5, 1024),
+                                 (129, 100), (300, 312), (64, 640), (33, 896)])     # lanes idle: VPL 1 / 3 / 5->6 / 7->8 tails
 def test_layernorm_fwd_bwd(lib, op, M, H):
     g = torch.Generator().manual_seed(M + H)
     s = torch.randn(M, H, generator=g) * 2 + 0.3
@@ -256,6 +259,172 @@ def test_layernorm_fwd_bwd(lib, op, M, H):
     torch.testing.assert_close(ds.cpu(), sr.grad, rtol=2e-2, atol=2e-2 * sr.grad.abs().max().item())
     torch.testing.assert_close(db.cpu(), br.grad, rtol=1e-4, atol=1e-4 * math.sqrt(M))
     torch.testing.assert_close(dg.cpu(), gr.grad, rtol=1e-2, atol=1e-2 * math.sqrt(M))
+
+
+@pytest.mark.parametrize("M", [1, 37, 4099])
+def test_layernorm_fwd_bwd_two_columns(lib, op, M):
+    """H = 2, one active lane per row: the checks of test_layernorm_fwd_bwd at its tolerances, except that ds is bounded by
+    rstd * max|gamma dy| per row instead of by max|ds|. With two columns x-hat = +-1 and the two terms of ds cancel
+    exactly (the true ds is ~eps-sized), so max|ds| is no scale; the 2^-9 perturbation of the stored xhat acts on terms of
+    size rstd * |gamma dy|."""
+    H = 2
+    g = torch.Generator().manual_seed(M + H)
+    s = torch.randn(M, H, generator=g) * 2 + 0.3
+    gamma = 1 + 0.1 * torch.randn(H, generator=g)
+    beta = 0.1 * torch.randn(H, generator=g)
+    dy = torch.randn(M, H, generator=g)
+    sr = s.clone().requires_grad_(True)
+    gr, br = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    yref = torch.nn.functional.layer_norm(sr, (H,), gr, br, 1e-12)
+    (yref * dy).sum().backward()
+    y = torch.empty(M, H, device="cuda")
+    yb = torch.empty(M, H, dtype=OPDT[op], device="cuda")
+    xh = torch.empty(M, H, dtype=OPDT[op], device="cuda")
+    rs = torch.empty(M, device="cuda")
+    sd, gd, bd, dyd = dev(s), dev(gamma), dev(beta), dev(dy)
+    _lib.check(kf(lib, "qst_ln_fwd", op)(sd.data_ptr(), gd.data_ptr(), bd.data_ptr(), 1e-12, M, H, y.data_ptr(),
+                              yb.data_ptr(), xh.data_ptr(), rs.data_ptr(), stream()))
+    torch.testing.assert_close(y.cpu(), yref.detach(), rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(yb.float().cpu(), yref.detach(), rtol=8e-3, atol=1e-2)
+    ds = torch.empty(M, H, device="cuda")
+    dsb = torch.empty(M, H, dtype=OPDT[op], device="cuda")
+    dg, db = torch.zeros(H, device="cuda"), torch.zeros(H, device="cuda")
+    scratch = torch.empty(lib.qst_ln_bwd_scratch_bytes(M, H) // 4, device="cuda")
+    _lib.check(kf(lib, "qst_ln_bwd", op)(dyd.data_ptr(), xh.data_ptr(), rs.data_ptr(), gd.data_ptr(), M, H, ds.data_ptr(),
+                              dsb.data_ptr(), dg.data_ptr(), db.data_ptr(), scratch.data_ptr(), stream()))
+    scale = rs.cpu()[:, None] * (gamma * dy).abs().amax(-1, keepdim=True)
+    assert bool(((ds.cpu() - sr.grad).abs() <= 2e-2 * sr.grad.abs() + 2e-2 * scale).all())
+    torch.testing.assert_close(db.cpu(), br.grad, rtol=1e-4, atol=1e-4 * math.sqrt(M))
+    torch.testing.assert_close(dg.cpu(), gr.grad, rtol=1e-2, atol=1e-2 * math.sqrt(M))
+
+
+# ------------------------------------------------------------------ dispatch targets, called by name
+# qst_gemm_nt / qst_gemm_nt_ln / qst_gemm_tn_group pick these kernels by shape or by qst_gemm8_mode and fall back silently
+# to the tiled kernels where a shape is turned down; called directly, a shape the kernel refuses fails the test instead.
+@pytest.mark.parametrize("tile", [0, 1], ids=["128x384", "256x256"])
+@pytest.mark.parametrize("M,N,K", [(256, 384, 384), (200, 192, 128), (1000, 1152, 384), (5000, 1536, 384)])
+def test_gemm_nt8_direct(lib, op, tile, M, N, K):
+    """qst_gemm_nt8 in both tiles and every epilogue qst_gemm_nt8_supported accepts (0 - 4), against the references and
+    tolerances of test_gemm_nt_epilogues"""
+    g = torch.Generator().manual_seed(M + N + K + tile)
+    A = opr(op, torch.randn(M, K, generator=g))
+    B = opr(op, torch.randn(N, K, generator=g) * 0.05)
+    bias = torch.randn(N, generator=g)
+    resid = torch.randn(M, N, generator=g)
+    ref = A @ B.t() + bias
+    Ad, Bd, biasd, residd = dev(A.to(OPDT[op])), dev(B.to(OPDT[op])), dev(bias), dev(resid)
+    nt8 = kf(lib, "qst_gemm_nt8", op)
+    base = dict(A=Ad, B=Bd, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, ldr=N)
+    for epi in range(5):
+        assert kf(lib, "qst_gemm_nt8_supported", op)(gemm_args(**base, resid=residd), epi) == 1, epi
+    assert kf(lib, "qst_gemm_nt8_supported", op)(gemm_args(**base), 5) == 0
+    Cb = torch.empty(M, N, dtype=OPDT[op], device="cuda")
+    _lib.check(nt8(gemm_args(**base, C=Cb, bias=biasd), 0, tile, stream()))
+    torch.testing.assert_close(Cb.float().cpu(), ref, rtol=8e-3, atol=2e-2)
+    Cf = torch.empty(M, N, dtype=torch.float32, device="cuda")
+    _lib.check(nt8(gemm_args(**base, C=Cf, bias=biasd, resid=residd), 1, tile, stream()))
+    torch.testing.assert_close(Cf.cpu(), ref + resid, rtol=1e-4, atol=1e-3)
+    C2 = torch.empty(M, N, dtype=OPDT[op], device="cuda")
+    _lib.check(nt8(gemm_args(**base, C=Cb, C2=C2, bias=biasd), 2, tile, stream()))
+    ur = ref.clone().requires_grad_(True)
+    torch.nn.functional.gelu(ur).sum().backward()
+    torch.testing.assert_close(Cb.float().cpu(), ur.grad, rtol=8e-3, atol=2e-2)
+    torch.testing.assert_close(C2.float().cpu(), torch.nn.functional.gelu(ref), rtol=8e-3, atol=2e-2)
+    gp = opr(op, torch.rand(M, N, generator=g) * 1.2 - 0.1)
+    _lib.check(nt8(gemm_args(**base, C=Cb, aux=dev(gp.to(OPDT[op]))), 3, tile, stream()))
+    torch.testing.assert_close(Cb.float().cpu(), (A @ B.t()) * gp, rtol=8e-3, atol=2e-2)
+    Cf.fill_(float("nan"))
+    _lib.check(nt8(gemm_args(**base, C=Cf, C2=C2, bias=biasd, resid=residd), 4, tile, stream()))
+    torch.testing.assert_close(Cf.cpu(), ref + resid, rtol=1e-4, atol=1e-3)
+    torch.testing.assert_close(C2.float().cpu(), ref + resid, rtol=8e-3, atol=2e-2)
+    assert torch.equal(C2, Cf.to(OPDT[op]))                     # the 16-bit copy is the rounding of the fp32 result
+
+
+@pytest.mark.parametrize("M,K,N", [(600, 128, 512), (300, 768, 768), (257, 64, 1024), (1000, 3072, 768)])
+def test_gemm_nt8_ln_direct(lib, op, M, K, N):
+    """qst_gemm_nt8_ln, modes 0 and 1, against the unfused qst_gemm_nt + qst_ln_fwd / qst_ln_bwd as in
+    test_gemm_nt_fused_layernorm; partials sized from qst_gemm_nt8_ln_block_rows"""
+    assert kf(lib, "qst_gemm_nt8_ln_supported", op)(N) == 1
+    g = torch.Generator().manual_seed(M + K + N)
+    Ad = dev(opr(op, torch.randn(M, K, generator=g)).to(OPDT[op]))
+    Bd = dev(opr(op, torch.randn(N, K, generator=g) * 0.05).to(OPDT[op]))
+    bias, resid = dev(torch.randn(N, generator=g)), dev(torch.randn(M, N, generator=g))
+    gamma, beta = dev(1 + 0.1 * torch.randn(N, generator=g)), dev(0.1 * torch.randn(N, generator=g))
+    eps = 1e-12
+
+    def ln_epi(**kw):
+        e = _lib.QstLnEpi()
+        e._keep = [v for v in kw.values() if torch.is_tensor(v)]
+        for k, v in kw.items():
+            setattr(e, k, v.data_ptr() if torch.is_tensor(v) else v)
+        return e
+
+    def f32(*shape):
+        return torch.empty(*shape, dtype=torch.float32, device="cuda")
+
+    def b16(*shape):
+        return torch.empty(*shape, dtype=OPDT[op], device="cuda")
+
+    base = dict(A=Ad, B=Bd, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, ldr=N)
+    s = f32(M, N)
+    _lib.check(kf(lib, "qst_gemm_nt", op)(gemm_args(**base, C=s, bias=bias, resid=resid), 1, stream()))
+    y0, yb0, xh0, rs0 = f32(M, N), b16(M, N), b16(M, N), f32(M)
+    _lib.check(kf(lib, "qst_ln_fwd", op)(s.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, M, N, y0.data_ptr(), yb0.data_ptr(),
+                              xh0.data_ptr(), rs0.data_ptr(), stream()))
+    y1, yb1, xh1, rs1 = f32(M, N), b16(M, N), b16(M, N), f32(M)
+    _lib.check(kf(lib, "qst_gemm_nt8_ln", op)(gemm_args(**base, C=y1, C2=yb1, bias=bias, resid=resid),
+                                   ln_epi(gamma=gamma, beta=beta, eps=eps, xhat=xh1, rstd=rs1), 0, stream()))
+    torch.testing.assert_close(y1, y0, rtol=1e-4, atol=1e-4)
+    torch.testing.assert_close(rs1, rs0, rtol=1e-5, atol=0)
+    torch.testing.assert_close(yb1.float(), yb0.float(), rtol=8e-3, atol=1e-2)
+    torch.testing.assert_close(xh1.float(), xh0.float(), rtol=8e-3, atol=1e-2)
+    dy = f32(M, N)
+    _lib.check(kf(lib, "qst_gemm_nt", op)(gemm_args(**base, C=dy, resid=resid), 1, stream()))
+    ds0, dsb0 = f32(M, N), b16(M, N)
+    dg0, db0 = torch.zeros(N, device="cuda"), torch.zeros(N, device="cuda")
+    scratch = torch.empty(lib.qst_ln_bwd_scratch_bytes(M, N) // 4, device="cuda")
+    _lib.check(kf(lib, "qst_ln_bwd", op)(dy.data_ptr(), xh0.data_ptr(), rs0.data_ptr(), gamma.data_ptr(), M, N, ds0.data_ptr(),
+                              dsb0.data_ptr(), dg0.data_ptr(), db0.data_ptr(), scratch.data_ptr(), stream()))
+    br = kf(lib, "qst_gemm_nt8_ln_block_rows", op)(M, N)
+    part = torch.full(((M + br - 1) // br, 2, N), float("nan"), device="cuda")
+    ds1, dsb1 = f32(M, N), b16(M, N)
+    _lib.check(kf(lib, "qst_gemm_nt8_ln", op)(gemm_args(**base, C=ds1, C2=dsb1, resid=resid),
+                                   ln_epi(gamma=gamma, xhat=xh0, rstd=rs0, partials=part), 1, stream()))
+    scale = ds0.abs().max().item()
+    torch.testing.assert_close(ds1, ds0, rtol=1e-4, atol=1e-4 * scale)
+    torch.testing.assert_close(dsb1.float(), dsb0.float(), rtol=8e-3, atol=1e-2 * scale)
+    torch.testing.assert_close(part[:, 0].sum(0), dg0, rtol=1e-4, atol=1e-4 * math.sqrt(M) * dy.abs().max().item())
+    torch.testing.assert_close(part[:, 1].sum(0), db0, rtol=1e-4, atol=1e-4 * math.sqrt(M) * dy.abs().max().item())
+    assert kf(lib, "qst_gemm_nt8_ln_timeouts", op)() == 0
+
+
+@pytest.mark.parametrize("M", [1000, 96, 32 * 70 + 32])
+def test_gemm_tn8_group_direct(lib, op, M):
+    """qst_gemm_tn8_group on the weight gradients of a MiniLM-shaped layer against the fp32 reference of
+    test_gemm_tn_group_matches_individual"""
+    H, I = 384, 1536
+    g = torch.Generator().manual_seed(9 + M)
+    shapes = [(H, I), (I, H), (H, H), (3 * H, H)]
+    grp = _lib.QstTnGroup()
+    grp.nprob, grp.splits = 4, 0
+    keep, refs, outs = [], [], []
+    for i, (N, K) in enumerate(shapes):
+        A = opr(op, torch.randn(M, N, generator=g))
+        B = opr(op, torch.randn(M, K, generator=g))
+        Ad, Bd = dev(A.to(OPDT[op])), dev(B.to(OPDT[op]))
+        Cm = torch.ones(N, K, device="cuda")
+        cs = torch.zeros(N, device="cuda")
+        q = grp.prob[i]
+        q.A, q.B, q.C, q.colsum = Ad.data_ptr(), Bd.data_ptr(), Cm.data_ptr(), cs.data_ptr()
+        q.M, q.N, q.K, q.lda, q.ldb, q.ldc = M, N, K, N, K, K
+        keep += [Ad, Bd]
+        refs.append((A.t() @ B + 1.0, A.sum(0)))
+        outs.append((Cm, cs))
+    _lib.check(kf(lib, "qst_gemm_tn8_group", op)(grp, stream()))
+    torch.cuda.synchronize()
+    for (Cm, cs), (rC, rcs) in zip(outs, refs):
+        torch.testing.assert_close(Cm.cpu(), rC, rtol=1e-3, atol=1e-3 * math.sqrt(M))
+        torch.testing.assert_close(cs.cpu(), rcs, rtol=1e-3, atol=1e-3 * math.sqrt(M))
 
 
 @pytest.mark.parametrize("M,K,N", [(128, 64, 384), (300, 384, 384), (1000, 1536, 384), (4096, 1152, 384),
