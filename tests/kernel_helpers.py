@@ -1,0 +1,157 @@
+"""What the GPU test files (tests/test_gpu_*.py) share, once each; imported like cross_encoder_fixtures, not a conftest.
+
+  * plumbing: the `lib` and `op` fixtures (`from kernel_helpers import lib, op  # noqa: F401`), stream / ptr, the operand
+    types (OPDT, opr, kf) and the ctypes argument structs filled from keywords (gemm_args, ln_epi, ffn_args, attn_desc);
+  * references and layouts more than one file compares against: attn_ref, the dropout state / descriptor, the MX scale
+    layout (stage_major, row_major);
+  * the encoder harness: quad_batch and run_step, one training forward + quadruplet loss + backward of a fresh HipEncoder.
+
+The rule: a helper lives in the test file that uses it; its second user moves it here instead of copying it. What a test
+asserts stays in its own file. tests/test_kernel_coverage_host.py reads the test files, not this module: an entry point is
+called by name (`lib.NAME`, `kf(lib, "NAME", op)`) from a test, never only from here.
+"""
+import math
+
+import pytest
+import torch
+
+from oracle import dropout_ref as D
+from quadruplet_sentence_transformer_amd import _lib
+from quadruplet_sentence_transformer_amd.encoder import HipEncoder, quadruplet_loss_raw, stacked
+
+
+@pytest.fixture(scope="module")
+def lib():
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return _lib.load()
+
+
+# The kernels with 16-bit matrix-core operands exist on bf16 (qst_*) and on IEEE half (qst_*_f16: QST_PREC_F16, the same
+# sources compiled on the other operand type); their tests run on both.
+OPDT = {"bf16": torch.bfloat16, "f16": torch.float16}
+
+
+@pytest.fixture(params=["bf16", "f16"])
+def op(request):
+    return request.param
+
+
+def stream():
+    return _lib.current_stream_ptr()
+
+
+ptr = _lib.ptr                       # data_ptr of a tensor, None for None
+
+
+def kf(lib, name, op):
+    return _lib.kfn(lib, name, op)
+
+
+def opr(op, t):
+    """t rounded to the operand type and back (what the kernel's operand holds)."""
+    return t.to(OPDT[op]).to(torch.float32)
+
+
+# ------------------------------------------------------------------ argument structs
+def filled(struct, **kw):
+    """struct() with its fields set from keywords; a tensor gives its data pointer and stays referenced by the struct, so the
+    device memory lives until the launch that takes the struct is enqueued."""
+    s = struct()
+    s._keep = [v for v in kw.values() if torch.is_tensor(v)]
+    for k, v in kw.items():
+        setattr(s, k, v.data_ptr() if torch.is_tensor(v) else v)
+    return s
+
+
+def gemm_args(**kw):
+    return filled(_lib.QstGemmArgs, **kw)
+
+
+def ln_epi(**kw):
+    return filled(_lib.QstLnEpi, **kw)
+
+
+def ffn_args(**kw):
+    return filled(_lib.QstFfnArgs, **kw)
+
+
+def attn_desc(**kw):
+    return filled(_lib.QstAttnDesc, **kw)
+
+
+# ------------------------------------------------------------------ references
+def attn_ref(qkv, mask, rel, n, L, A, d, pm=None):
+    """HF attention (modeling_bert.py BertSelfAttention; MPNet adds the position bias `rel` [A, L, L] before the mask) in the
+    dtype of qkv, fp32 or fp64; pm [n, A, L, L]: dropout multipliers of the probabilities."""
+    H = A * d
+    q, k, v = [t.view(n, L, A, d).transpose(1, 2) for t in qkv.view(n, L, 3 * H).split(H, dim=-1)]
+    s = q @ k.transpose(-1, -2) / math.sqrt(d)
+    if rel is not None:
+        s = s + rel[None]
+    s = s + (1.0 - mask[:, None, None, :].to(qkv.dtype)) * torch.finfo(torch.float32).min
+    p = torch.softmax(s, -1)
+    if pm is not None:
+        p = p * pm
+    return (p @ v).transpose(1, 2).reshape(n * L, H)
+
+
+def drop_state(lib, seed, step):
+    """The four-word dropout state of `seed` after `step` advances, built by the library's own init / advance launches."""
+    st = torch.zeros(4, dtype=torch.int32, device="cuda")
+    _lib.check(lib.qst_dropout_init(st.data_ptr(), seed, stream()))
+    for _ in range(step):
+        _lib.check(lib.qst_dropout_advance(st.data_ptr(), stream()))
+    return st
+
+
+def drop_desc(st, site, p):
+    d = _lib.QstDrop()
+    d.state, d.site, d.thr16 = st.data_ptr(), site, D.thr16_of(p)
+    return d
+
+
+def stage_major(s_rowmajor):
+    """[rows, K/32] scale bytes -> the library's layout [ceil(K/128)][rows][4] (zero-padded), flattened."""
+    rows, nb = s_rowmajor.shape
+    pad = (-nb) % 4
+    t = torch.nn.functional.pad(s_rowmajor, (0, pad))
+    return t.view(rows, (nb + pad) // 4, 4).permute(1, 0, 2).contiguous().view(-1)
+
+
+def row_major(s_stage, rows, K):
+    nb = K // 32
+    return s_stage.view((nb + 3) // 4, rows, 4).permute(1, 0, 2).reshape(rows, -1)[:, :nb]
+
+
+# ------------------------------------------------------------------ encoder harness
+def quad_batch(cfg, ids, mask, types, B, L):
+    """The quadruplet batch (numpy or torch, 4 * B * L elements each) as the [4B, L] device tensors HipEncoder takes; no type
+    ids for a model without a token-type table."""
+    idd, mdd, tdd = [torch.as_tensor(x).view(4 * B, L).cuda() for x in (ids, mask, types)]
+    return idd, mdd, (tdd if cfg.type_vocab_size else None)
+
+
+def run_step(cfg, arena, ids, mask, types, B, L, precision="bf16", want_grads=True, scale=None, want_tokens=False, setup=None):
+    """A fresh HipEncoder on `arena` (setup(enc), if given, runs before the forward: dropout, fusion switches), one training
+    forward at `precision`, the quadruplet loss at the reference's settings and, with want_grads, the backward under the loss
+    scale `scale`. Returns the loss (float), the embeddings [4, B, D] and the UNSCALED gradient arena (None without
+    want_grads) on the CPU, and the encoder."""
+    enc = HipEncoder(cfg)
+    enc.load_arena(arena)
+    if setup is not None:
+        setup(enc)
+    idd, mdd, tdd = quad_batch(cfg, ids, mask, types, B, L)
+    emb, _, saved = enc.forward(idd, mdd, tdd, training=True, want_tokens=want_tokens, precision=precision)
+    e4 = emb.view(4, B, -1)
+    gout = None if scale is None else torch.tensor([float(scale)], dtype=torch.float32, device="cuda")
+    loss, g = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2, grad_out=gout,
+                                  want_grads=want_grads)
+    grads = None
+    if want_grads:
+        enc.ensure_train_state()
+        enc.grads.zero_()
+        enc.backward(idd, mdd, tdd, stacked(g), saved, precision=precision)
+        grads = enc.grads.cpu()
+        if scale is not None:
+            grads = grads / float(scale)
+    return loss.item(), e4.cpu(), grads, enc

@@ -20,31 +20,10 @@ from quadruplet_sentence_transformer_amd import _lib  # noqa: E402
 from quadruplet_sentence_transformer_amd.config import PRESETS  # noqa: E402
 from quadruplet_sentence_transformer_amd.encoder import HipEncoder  # noqa: E402
 from quadruplet_sentence_transformer_amd.synthetic import synthetic_params, synthetic_quadruplets  # noqa: E402
+from kernel_helpers import (OPDT, attn_desc, attn_ref, drop_desc, drop_state, gemm_args, kf, lib, ln_epi, opr,  # noqa: E402,F401
+                            stream)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-def stream():
-    return _lib.current_stream_ptr()
-
-
-def make_state(lib, seed, step):
-    st = torch.zeros(4, dtype=torch.int32, device="cuda")
-    _lib.check(lib.qst_dropout_init(st.data_ptr(), seed, stream()))
-    for _ in range(step):
-        _lib.check(lib.qst_dropout_advance(st.data_ptr(), stream()))
-    return st
-
-
-def drop(st, site, p):
-    d = _lib.QstDrop()
-    d.state, d.site, d.thr16 = st.data_ptr(), site, D.thr16_of(p)
-    return d
 
 
 def mult(seed, step, site, shape, p):
@@ -54,25 +33,16 @@ def mult(seed, step, site, shape, p):
 @pytest.mark.parametrize("seed,step,site,n,p", [(0, 0, 0, 1000, 0.1), (1234567890123456789, 3, D.SITE_EMBED, 99999, 0.1),
                                                 (7, 1000, D.site_probs(11), 1 << 20, 0.37), (2 ** 40 + 5, 2, 5, 7, 0.5)])
 def test_mask_words_equal_the_oracle(lib, seed, step, site, n, p):
-    st = make_state(lib, seed, step)
+    st = torch.zeros(4, dtype=torch.int32, device="cuda")
+    _lib.check(lib.qst_dropout_init(st.data_ptr(), seed, stream()))
+    for _ in range(step):
+        _lib.check(lib.qst_dropout_advance(st.data_ptr(), stream()))
     out = torch.empty(n, device="cuda")
-    _lib.check(lib.qst_dropout_multipliers(drop(st, site, p), 0, n, out.data_ptr(), stream()))
+    _lib.check(lib.qst_dropout_multipliers(drop_desc(st, site, p), 0, n, out.data_ptr(), stream()))
     assert np.array_equal(out.cpu().numpy(), D.multipliers(seed, step, site, n, p))
-    _lib.check(lib.qst_dropout_multipliers(drop(st, site, p), 1, n, out.data_ptr(), stream()))      # the attention-probability form
+    _lib.check(lib.qst_dropout_multipliers(drop_desc(st, site, p), 1, n, out.data_ptr(), stream()))      # the attention-probability form
     assert np.array_equal(out.cpu().numpy(), D.multipliers8(seed, step, site, n, p))
     assert st.cpu().tolist()[2] == step
-
-
-def bfr(t):
-    return t.to(torch.bfloat16).to(torch.float32)
-
-
-def opr(dt, t):
-    """t rounded to the 16-bit operand type dt and back"""
-    return t.to(dt).to(torch.float32)
-
-
-OPDT = {"bf16": torch.bfloat16, "f16": torch.float16}
 
 
 @pytest.mark.parametrize("M,H", [(37, 64), (300, 384), (129, 768)])
@@ -89,7 +59,7 @@ def row_kernels_apply_the_mask(lib, op, M, H):
     dt = OPDT[op]
     g = torch.Generator().manual_seed(M + H)
     seed, step, p = 99, 2, 0.2
-    st = make_state(lib, seed, step)
+    st = drop_state(lib, seed, step)
     mk = mult(seed, step, D.SITE_EMBED, (M, H), p).cuda()
     # embeddings + LayerNorm + dropout
     V, P = 50, 40
@@ -97,10 +67,10 @@ def row_kernels_apply_the_mask(lib, op, M, H):
     word = torch.randn(V, H, generator=g).cuda(); pemb = torch.randn(P, H, generator=g).cuda()
     gamma = (1 + 0.1 * torch.randn(H, generator=g)).cuda(); beta = (0.1 * torch.randn(H, generator=g)).cuda()
     outs = []
-    for d in (None, drop(st, D.SITE_EMBED, p)):
+    for d in (None, drop_desc(st, D.SITE_EMBED, p)):
         y = torch.empty(M, H, device="cuda"); yb = torch.empty(M, H, dtype=dt, device="cuda")
         xh = torch.empty(M, H, dtype=dt, device="cuda"); rs = torch.empty(M, device="cuda")
-        _lib.check(_lib.kfn(lib, "qst_embed_ln_fwd_drop", op)(ids.data_ptr(), None, pos.data_ptr(), word.data_ptr(), pemb.data_ptr(), None,
+        _lib.check(kf(lib, "qst_embed_ln_fwd_drop", op)(ids.data_ptr(), None, pos.data_ptr(), word.data_ptr(), pemb.data_ptr(), None,
                                              gamma.data_ptr(), beta.data_ptr(), 1e-12, M, H, y.data_ptr(), yb.data_ptr(),
                                              xh.data_ptr(), rs.data_ptr(), d, stream()))
         outs.append((y, yb, xh, rs))
@@ -110,11 +80,11 @@ def row_kernels_apply_the_mask(lib, op, M, H):
     # LayerNorm backward: mask on the incoming gradient (a dropout after the LayerNorm) / on the bf16 result only
     dy = torch.randn(M, H, generator=g).cuda()
     res = []
-    for dy_in, din, dout in ((dy, None, None), (dy * mk, None, None), (dy, drop(st, D.SITE_EMBED, p), None),
-                             (dy, None, drop(st, D.SITE_EMBED, p))):
+    for dy_in, din, dout in ((dy, None, None), (dy * mk, None, None), (dy, drop_desc(st, D.SITE_EMBED, p), None),
+                             (dy, None, drop_desc(st, D.SITE_EMBED, p))):
         ds = torch.empty(M, H, device="cuda"); dsb = torch.empty(M, H, dtype=dt, device="cuda")
         dg = torch.zeros(H, device="cuda"); db = torch.zeros(H, device="cuda")
-        _lib.check(_lib.kfn(lib, "qst_ln_bwd_drop", op)(dy_in.data_ptr(), xh0.data_ptr(), rs0.data_ptr(), gamma.data_ptr(), M, H, ds.data_ptr(),
+        _lib.check(kf(lib, "qst_ln_bwd_drop", op)(dy_in.data_ptr(), xh0.data_ptr(), rs0.data_ptr(), gamma.data_ptr(), M, H, ds.data_ptr(),
                                        dsb.data_ptr(), dg.data_ptr(), db.data_ptr(), None, din, dout, stream()))
         torch.cuda.synchronize()
         res.append((ds, dsb, dg, db))
@@ -133,41 +103,34 @@ def test_projection_epilogues_apply_the_mask(lib, M, K, N):
     gradient (where 3)."""
     g = torch.Generator().manual_seed(M + K)
     seed, step, p, site = 5, 1, 0.1, D.site_ffn_out(3)
-    st = make_state(lib, seed, step)
+    st = drop_state(lib, seed, step)
     mk = mult(seed, step, site, (M, N), p)
-    A = bfr(torch.randn(M, K, generator=g)); B = bfr(torch.randn(N, K, generator=g) * 0.05)
+    A = opr("bf16", torch.randn(M, K, generator=g)); B = opr("bf16", torch.randn(N, K, generator=g) * 0.05)
     bias = torch.randn(N, generator=g); resid = torch.randn(M, N, generator=g)
     gamma = 1 + 0.1 * torch.randn(N, generator=g); beta = 0.1 * torch.randn(N, generator=g)
     Ad, Bd = A.to(torch.bfloat16).cuda(), B.to(torch.bfloat16).cuda()
     biasd, residd, gd, bd = bias.cuda(), resid.cuda(), gamma.cuda(), beta.cuda()
 
     def args(**kw):
-        ga = _lib.QstGemmArgs()
-        ga.A, ga.B, ga.M, ga.N, ga.K, ga.lda, ga.ldb, ga.ldc, ga.ldr = Ad.data_ptr(), Bd.data_ptr(), M, N, K, K, K, N, N
-        ga.resid = residd.data_ptr()
-        for k, v in kw.items():
-            setattr(ga, k, v)
-        return ga
+        return gemm_args(A=Ad, B=Bd, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, ldr=N, resid=residd, **kw)
     v = (A @ B.t() + bias) * mk + resid
     C = torch.empty(M, N, device="cuda")
-    _lib.check(lib.qst_gemm_nt(args(C=C.data_ptr(), bias=biasd.data_ptr(), drop=drop(st, site, p), drop_where=1), 1, stream()))
+    _lib.check(lib.qst_gemm_nt(args(C=C.data_ptr(), bias=biasd.data_ptr(), drop=drop_desc(st, site, p), drop_where=1), 1, stream()))
     torch.testing.assert_close(C.cpu(), v, rtol=1e-4, atol=1e-3)
     # fused forward LayerNorm
-    ln = _lib.QstLnEpi()
     xh = torch.empty(M, N, dtype=torch.bfloat16, device="cuda"); rs = torch.empty(M, device="cuda")
     C2 = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
-    ln.gamma, ln.beta, ln.eps, ln.xhat, ln.rstd = gd.data_ptr(), bd.data_ptr(), 1e-12, xh.data_ptr(), rs.data_ptr()
-    _lib.check(lib.qst_gemm_nt_ln(args(C=C.data_ptr(), C2=C2.data_ptr(), bias=biasd.data_ptr(), drop=drop(st, site, p), drop_where=1),
+    ln = ln_epi(gamma=gd, beta=bd, eps=1e-12, xhat=xh, rstd=rs)
+    _lib.check(lib.qst_gemm_nt_ln(args(C=C.data_ptr(), C2=C2.data_ptr(), bias=biasd.data_ptr(), drop=drop_desc(st, site, p), drop_where=1),
                                   ln, 0, stream()))
     ref = torch.nn.functional.layer_norm(v, (N,), gamma, beta, 1e-12)
     torch.testing.assert_close(C.cpu(), ref, rtol=1e-3, atol=2e-3)
     # fused LayerNorm backward
-    xhat = bfr(torch.randn(M, N, generator=g)); rstd = torch.rand(M, generator=g) + 0.5
+    xhat = opr("bf16", torch.randn(M, N, generator=g)); rstd = torch.rand(M, generator=g) + 0.5
     xhd, rsd = xhat.to(torch.bfloat16).cuda(), rstd.cuda()
-    ln2 = _lib.QstLnEpi()
     br = lib.qst_gemm_nt_ln_block_rows_m(N, M)
     part = torch.zeros((M + br - 1) // br, 2, N, device="cuda")
-    ln2.gamma, ln2.xhat, ln2.rstd, ln2.partials = gd.data_ptr(), xhd.data_ptr(), rsd.data_ptr(), part.data_ptr()
+    ln2 = ln_epi(gamma=gd, xhat=xhd, rstd=rsd, partials=part)
 
     def ln_bwd_ref(dy):
         dx = dy * gamma
@@ -175,24 +138,14 @@ def test_projection_epilogues_apply_the_mask(lib, M, K, N):
     dy = A @ B.t() + resid
     for where, want_c, want_c2, want_dgamma in ((2, ln_bwd_ref(dy), ln_bwd_ref(dy) * mk, (dy * xhat).sum(0)),
                                                 (3, ln_bwd_ref(dy * mk), ln_bwd_ref(dy * mk), (dy * mk * xhat).sum(0))):
-        _lib.check(lib.qst_gemm_nt_ln(args(C=C.data_ptr(), C2=C2.data_ptr(), drop=drop(st, site, p), drop_where=where), ln2, 1, stream()))
+        _lib.check(lib.qst_gemm_nt_ln(args(C=C.data_ptr(), C2=C2.data_ptr(), drop=drop_desc(st, site, p), drop_where=where), ln2, 1, stream()))
         torch.testing.assert_close(C.cpu(), want_c, rtol=1e-3, atol=2e-3)
         torch.testing.assert_close(C2.float().cpu(), want_c2, rtol=1e-2, atol=1e-2)
         assert ((C2.float().cpu() == 0) == (want_c2 == 0)).float().mean() > 0.999      # zeros exactly where the mask is (where 2)
         torch.testing.assert_close(part[:, 0].sum(0).cpu(), want_dgamma, rtol=1e-3, atol=1e-3 * math.sqrt(M) * 4)
     # a mask description the kernel cannot honour is refused
-    assert lib.qst_gemm_nt(args(C=C.data_ptr(), drop=drop(st, site, p), drop_where=2), 1, stream()) != 0
-    assert lib.qst_gemm_nt_ln(args(C=C.data_ptr(), drop=drop(st, site, p), drop_where=1), ln2, 1, stream()) != 0
-
-
-def attn_ref(qkv, mask, rel, n, L, A, d, pm):
-    H = A * d
-    q, k, v = [t.view(n, L, A, d).transpose(1, 2) for t in qkv.view(n, L, 3 * H).split(H, dim=-1)]
-    s = q @ k.transpose(-1, -2) / math.sqrt(d)
-    if rel is not None:
-        s = s + rel[None]
-    s = s + (1.0 - mask[:, None, None, :].float()) * torch.finfo(torch.float32).min
-    return ((torch.softmax(s, -1) * pm) @ v).transpose(1, 2).reshape(n * L, H)
+    assert lib.qst_gemm_nt(args(C=C.data_ptr(), drop=drop_desc(st, site, p), drop_where=2), 1, stream()) != 0
+    assert lib.qst_gemm_nt_ln(args(C=C.data_ptr(), drop=drop_desc(st, site, p), drop_where=1), ln2, 1, stream()) != 0
 
 
 @pytest.mark.parametrize("n,L,A,d,use_rel", [(2, 32, 2, 32, False), (3, 128, 12, 32, False), (2, 160, 2, 64, True),
@@ -217,14 +170,14 @@ def attention_with_dropped_probabilities(lib, op, n, L, A, d, use_rel):
     H = A * d
     g = torch.Generator().manual_seed(n * L + A + d)
     seed, step, p, site = 31337, 4, 0.1, D.site_probs(1)
-    st = make_state(lib, seed, step)
+    st = drop_state(lib, seed, step)
     pm = torch.from_numpy(D.multipliers8(seed, step, site, n * A * L * L, p).reshape(n, A, L, L))
-    qkv = opr(dt, torch.randn(n * L, 3 * H, generator=g))
+    qkv = opr(op, torch.randn(n * L, 3 * H, generator=g))
     lens = torch.randint(max(1, L // 8), L + 1, (n,), generator=g); lens[0] = L
     mask = (torch.arange(L)[None, :] < lens[:, None]).long()
     relpos = (0.5 * torch.randn(A, 2 * L, generator=g)) if use_rel else None
     ridx = (torch.arange(L)[None, :] - torch.arange(L)[:, None]) + L
-    dctx = opr(dt, torch.randn(n * L, H, generator=g))
+    dctx = opr(op, torch.randn(n * L, H, generator=g))
     qr = qkv.clone().requires_grad_(True)
     relr = relpos.clone().requires_grad_(True) if use_rel else None
     ref = attn_ref(qr, mask, relr[:, ridx] if use_rel else None, n, L, A, d, pm)
@@ -232,24 +185,22 @@ def attention_with_dropped_probabilities(lib, op, n, L, A, d, use_rel):
 
     qd = qkv.to(dt).cuda(); md = mask.cuda(); reld = relpos.cuda() if use_rel else None
     ctx = torch.empty(n * L, H, dtype=dt, device="cuda"); lse = torch.empty(n, A, L, device="cuda")
-    q = _lib.QstAttnDesc()
-    q.qkv, q.mask, q.rel_pos, q.nseq, q.L, q.A, q.d = qd.data_ptr(), md.data_ptr(), _lib.ptr(reld), n, L, A, d
-    q.ctx, q.lse, q.drop = ctx.data_ptr(), lse.data_ptr(), drop(st, site, p)
-    _lib.check(_lib.kfn(lib, "qst_attention_fwd_ex", op)(q, stream()))
+    q = attn_desc(qkv=qd, mask=md, rel_pos=reld, nseq=n, L=L, A=A, d=d, ctx=ctx, lse=lse, drop=drop_desc(st, site, p))
+    _lib.check(kf(lib, "qst_attention_fwd_ex", op)(q, stream()))
     torch.testing.assert_close(ctx.float().cpu(), ref.detach(), rtol=2e-2, atol=2e-2)
     # lse is the log-sum-exp of the UNDROPPED scores: same as a forward without dropout
     q0 = _lib.QstAttnDesc.from_buffer_copy(q)
     q0.drop = _lib.QstDrop()
     ctx0 = torch.empty_like(ctx); lse0 = torch.empty_like(lse)
     q0.ctx, q0.lse = ctx0.data_ptr(), lse0.data_ptr()
-    _lib.check(_lib.kfn(lib, "qst_attention_fwd_ex", op)(q0, stream()))
+    _lib.check(kf(lib, "qst_attention_fwd_ex", op)(q0, stream()))
     assert torch.equal(lse, lse0) and not torch.equal(ctx, ctx0)
 
     dq = torch.empty(n * L * 3 * H, dtype=dt, device="cuda")
     drel = torch.zeros(A, 2 * L, device="cuda") if use_rel else None
     dcd = dctx.to(dt).cuda(); delta = torch.empty(n, A, L, device="cuda")
     q.dctx, q.dqkv, q.drel, q.delta_scratch = dcd.data_ptr(), dq.data_ptr(), _lib.ptr(drel), delta.data_ptr()
-    _lib.check(_lib.kfn(lib, "qst_attention_bwd_ex", op)(q, stream()))
+    _lib.check(kf(lib, "qst_attention_bwd_ex", op)(q, stream()))
     gref = qr.grad
     got = dq.view(n * L, 3 * H).float().cpu()
     assert (got - gref).abs().max().item() <= 3e-2 * max(1.0, gref.abs().max().item())
@@ -261,7 +212,7 @@ def attention_with_dropped_probabilities(lib, op, n, L, A, d, use_rel):
         drel2 = torch.zeros(A, 2 * L, device="cuda") if use_rel else None
         q.dqkv, q.drel = dq2.data_ptr(), _lib.ptr(drel2)
         q.force_split = 1
-        _lib.check(_lib.kfn(lib, "qst_attention_bwd_ex", op)(q, stream()))
+        _lib.check(kf(lib, "qst_attention_bwd_ex", op)(q, stream()))
         torch.cuda.synchronize()
         torch.testing.assert_close(dq.float(), dq2.float(), rtol=2e-2, atol=2e-2 * max(1.0, gref.abs().max().item()))
 

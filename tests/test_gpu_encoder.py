@@ -16,10 +16,11 @@ pytestmark = pytest.mark.gpu
 
 import quadruplet_sentence_transformer_amd as qst  # noqa: E402
 from quadruplet_sentence_transformer_amd.config import PRESETS, build_layout  # noqa: E402
-from quadruplet_sentence_transformer_amd.encoder import HipEncoder, quadruplet_loss_raw  # noqa: E402
+from quadruplet_sentence_transformer_amd.encoder import HipEncoder  # noqa: E402
 from quadruplet_sentence_transformer_amd.synthetic import synthetic_params, synthetic_quadruplets  # noqa: E402
 from quadruplet_sentence_transformer_amd import _lib  # noqa: E402
 from oracle import torch_ref as R  # noqa: E402
+from kernel_helpers import run_step  # noqa: E402
 
 # Gradient bounds (relative L2 error per parameter tensor) against the oracle that rounds the same GEMM operands to bf16 --
 # in the forward AND in the backward (dY, dO, P, dS enter its products bf16-rounded, as they enter the matrix cores; bias
@@ -75,36 +76,25 @@ def run_case(name, B, L, ragged, weights_kw, check_grads=True, emb_atol_vs_bf16_
         lossb.backward()
 
     # HIP
-    enc = HipEncoder(cfg)
-    enc.load_arena(arena)
-    if dropout is not None:
-        enc.set_dropout(dropout[0], dropout[1], dropout[2])
-    if ffn_chain is not None:
-        enc.set_ffn_chain(ffn_chain)
-    if ln_fusion is not None:
-        enc.set_ln_fusion(ln_fusion)
-    n = 4 * B
-    idd, mdd, tdd = ids_t.view(n, L).cuda(), mask_t.view(n, L).cuda(), types_t.view(n, L).cuda()
-    emb, tok, saved = enc.forward(idd, mdd, tdd if cfg.type_vocab_size else None, training=True, want_tokens=True)
-    e4 = emb.view(4, B, -1)
-    loss, g = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2, want_grads=True)
-    torch.cuda.synchronize()
+    def setup(enc):
+        if dropout is not None:
+            enc.set_dropout(dropout[0], dropout[1], dropout[2])
+        if ffn_chain is not None:
+            enc.set_ffn_chain(ffn_chain)
+        if ln_fusion is not None:
+            enc.set_ln_fusion(ln_fusion)
+    loss, emb, ga, enc = run_step(cfg, arena, ids_t, mask_t, types_t, B, L, want_grads=check_grads, want_tokens=True, setup=setup)
     assert torch.isfinite(emb).all()
     # models without the Normalize module (bare bert-base) emit un-normalised embeddings: scale the absolute
     # tolerances by the embedding magnitude so they mean the same thing as for unit-norm outputs
     sc = float(emb32.norm(dim=-1).mean()) if scale_by_emb else 1.0
-    torch.testing.assert_close(emb.cpu().view(4, B, -1), embb.detach(), rtol=1e-3, atol=emb_atol_vs_bf16_oracle * sc)
-    assert abs(loss.item() - lossb.item()) < max(1e-4, 0.3 * emb_atol_vs_bf16_oracle) * sc
-    assert abs(loss.item() - loss32.item()) < 1e-3 * sc
-    torch.testing.assert_close(emb.cpu().view(4, B, -1), emb32, rtol=0, atol=2e-3 * sc)
+    torch.testing.assert_close(emb, embb.detach(), rtol=1e-3, atol=emb_atol_vs_bf16_oracle * sc)
+    assert abs(loss - lossb.item()) < max(1e-4, 0.3 * emb_atol_vs_bf16_oracle) * sc
+    assert abs(loss - loss32.item()) < 1e-3 * sc
+    torch.testing.assert_close(emb, emb32, rtol=0, atol=2e-3 * sc)
 
     if check_grads:
-        enc.ensure_train_state()
-        enc.grads.zero_()
-        enc.backward(idd, mdd, tdd if cfg.type_vocab_size else None, torch.cat(g, 0), saved)
-        torch.cuda.synchronize()
         segs, _ = build_layout(cfg)
-        ga = enc.grads.cpu()
         worst = 0.0
         errs = []
         cls_max = {}
@@ -135,8 +125,8 @@ def run_case(name, B, L, ragged, weights_kw, check_grads=True, emb_atol_vs_bf16_
         print(f"[grad-cls] {name} B={B} L={L}: " + ", ".join(f"{k} {v:.2e}" for k, v in sorted(cls_max.items())))
         errs.sort(reverse=True)
         print(f"[grad-err] {name} B={B} L={L}: " + ", ".join(f"{n} {e:.2e}" for e, n in errs[:4]))
-        return loss.item(), worst
-    return loss.item(), None
+        return loss, worst
+    return loss, None
 
 
 @pytest.mark.parametrize("name,B,L,ragged", [("tiny-bert", 2, 32, False), ("tiny-bert", 3, 64, True),
@@ -343,24 +333,11 @@ def test_parity_precision_backward_matches_fp32_autograd(name, B, L, ragged, wkw
     loss32, emb32 = R.quadruplet_step(P, cfg, ids_t, mask_t, types_t if cfg.type_vocab_size else None, LOSS_KW, bf16_operands=False,
                                       dropout=masks)
     loss32.backward()
-    enc = HipEncoder(cfg)
-    enc.load_arena(arena)
-    enc.ensure_train_state()
-    if drop is not None:
-        enc.set_dropout(drop[0], drop[1], drop[2])
-    n = 4 * B
-    idd, mdd, tdd = ids_t.view(n, L).cuda(), mask_t.view(n, L).cuda(), types_t.view(n, L).cuda()
-    tdd = tdd if cfg.type_vocab_size else None
-    emb, _, saved = enc.forward(idd, mdd, tdd, training=True, precision="bf16x3")
-    e4 = emb.view(4, B, -1)
-    loss, g = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2, want_grads=True)
-    enc.grads.zero_()
-    enc.backward(idd, mdd, tdd, torch.cat(g, 0), saved, precision="bf16x3")
-    torch.cuda.synchronize()
-    torch.testing.assert_close(emb.cpu().view(4, B, -1), emb32.detach(), rtol=1e-3, atol=1e-4)
-    assert abs(loss.item() - loss32.item()) < 1e-5
+    loss, emb, ga, _ = run_step(cfg, arena, ids_t, mask_t, types_t, B, L, precision="bf16x3",
+                                setup=(lambda enc: enc.set_dropout(*drop)) if drop is not None else None)
+    torch.testing.assert_close(emb, emb32.detach(), rtol=1e-3, atol=1e-4)
+    assert abs(loss - loss32.item()) < 1e-5
     segs, _ = build_layout(cfg)
-    ga = enc.grads.cpu()
     worst = (0.0, "")
     gnorm = float(torch.sqrt(sum((P[s_.name].grad.double() ** 2).sum() for s_ in segs)))
     cls_top = {}

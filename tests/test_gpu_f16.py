@@ -29,6 +29,7 @@ from quadruplet_sentence_transformer_amd.synthetic import synthetic_params, synt
 from quadruplet_sentence_transformer_amd.trainer import QuadrupletTrainer, warmup_linear_lr  # noqa: E402
 from oracle import torch_ref as R  # noqa: E402
 from tests.test_oracle_golden import CLI, ENC_CASES, golden_inputs  # noqa: E402
+from kernel_helpers import gemm_args, ln_epi, quad_batch, run_step  # noqa: E402
 
 LOSS_KW = dict(gamma=0.6, margin_pos_neg=1.0, margin_pos_part=0.5, margin_part_neg=0.5, p=2.0, swap=False)
 ALL_CASES = ENC_CASES + [("minilm_l128", "all-MiniLM-L6-v2", 2, 128, dict(std=0.02), "norms")]
@@ -46,28 +47,10 @@ def enc_g(golden_dir):
     return np.load(os.path.join(golden_dir, "encoder_golden.npz"))
 
 
-def run_f16(cfg, arena, ids, mask, types, B, L, want_grads=True, scale=None, prec="f16"):
-    """One f16 training forward + loss (+ backward under the loss scale `scale`, gradients returned UNSCALED)."""
-    enc = HipEncoder(cfg)
-    enc.load_arena(arena)
-    n = 4 * B
-    idd = torch.from_numpy(ids).view(n, L).cuda()
-    mdd = torch.from_numpy(mask).view(n, L).cuda()
-    tdd = torch.from_numpy(types).view(n, L).cuda() if cfg.type_vocab_size else None
-    emb, _, saved = enc.forward(idd, mdd, tdd, training=True, precision=prec)
-    e4 = emb.view(4, B, -1)
-    gout = None
-    if scale is not None:
-        gout = torch.tensor([float(scale)], dtype=torch.float32, device="cuda")
-    loss, g = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2, grad_out=gout,
-                                  want_grads=want_grads)
-    ga = None
-    if want_grads:
-        enc.ensure_train_state()
-        enc.grads.zero_()
-        enc.backward(idd, mdd, tdd, stacked(g), saved, precision=prec)
-        ga = enc.grads.cpu().numpy() / (1.0 if scale is None else float(scale))
-    return loss.item(), e4.cpu().numpy(), ga, enc
+def run_f16(cfg, arena, ids, mask, types, B, L, scale=None, prec="f16"):
+    """run_step at an f16 precision, results as numpy"""
+    loss, e4, ga, enc = run_step(cfg, arena, ids, mask, types, B, L, precision=prec, scale=scale)
+    return loss, e4.numpy(), ga.numpy(), enc
 
 
 @pytest.mark.parametrize("prec", ["f16", "f16w"])
@@ -147,14 +130,6 @@ def test_f16_path_equals_the_f16_operand_oracle(name, B, L):
         assert np.linalg.norm(a - b) <= bound * np.linalg.norm(b) + 1e-8, (s.name, np.linalg.norm(a - b) / np.linalg.norm(b))
 
 
-def gemm_args(**kw):
-    g = _lib.QstGemmArgs()
-    g._keep = [v for v in kw.values() if torch.is_tensor(v)]
-    for k, v in kw.items():
-        setattr(g, k, v.data_ptr() if torch.is_tensor(v) else v)
-    return g
-
-
 @pytest.mark.parametrize("form", [0, 0x40], ids=["tiled", "eightphase"])
 def test_f16_forward_epilogues_saturate_and_backward_ones_overflow(form):
     """sat16 = 1 (what every forward launch of the f16 path sets): results beyond half's range leave as +-65,504; sat16 = 0
@@ -210,9 +185,7 @@ def test_split_weight_second_pass(M, N, K, form):
     err_hi = (ref_hi - ref).abs().max().item()
     assert err < 0.05 * err_hi + 2e-6 * math.sqrt(K), (err, err_hi)
     if N == 384:
-        e = _lib.QstLnEpi()
-        gamma, beta = torch.ones(N, device="cuda"), torch.zeros(N, device="cuda")
-        e.gamma, e.beta, e.eps = gamma.data_ptr(), beta.data_ptr(), 1e-12
+        e = ln_epi(gamma=torch.ones(N, device="cuda"), beta=torch.zeros(N, device="cuda"), eps=1e-12)
         Y = torch.empty(M, N, device="cuda")
         _lib.check(lib.qst_gemm_nt_ln_f16(gemm_args(A=Ad, B=Bh, B2=Bl, C=Y, bias=bias.cuda(), resid=resid.cuda(), M=M, N=N, K=K,
                                                     lda=K, ldb=K, ldc=N, ldr=N), e, 0, _lib.current_stream_ptr()))
@@ -270,8 +243,7 @@ def test_f16_gradients_survive_a_512_quadruplet_mean_loss():
     ids, mask, types = synthetic_quadruplets(cfg, B, L, seed=14, ragged=True)
     _, _, g_scaled, enc = run_f16(cfg, arena, ids, mask, types, B, L, scale=65536.0)
     _, _, g_plain, _ = run_f16(cfg, arena, ids, mask, types, B, L, scale=None)
-    n = 4 * B
-    idd, mdd, tdd = [torch.from_numpy(x).view(n, L).cuda() for x in (ids, mask, types)]
+    idd, mdd, tdd = quad_batch(cfg, ids, mask, types, B, L)
     emb, _, saved = enc.forward(idd, mdd, tdd, training=True, precision="bf16x3")
     e4 = emb.view(4, B, -1)
     _, g = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2, want_grads=True)
@@ -463,30 +435,16 @@ def check_against_fp32_autograd(name, B, L, ragged, wkw, drop, prec, layers=None
     loss32, emb32 = R.quadruplet_step(P, cfg, ids_t, mask_t, types_t if cfg.type_vocab_size else None, LOSS_KW, bf16_operands=False,
                                       dropout=masks)
     loss32.backward()
-    enc = HipEncoder(cfg)
-    enc.load_arena(arena)
-    enc.ensure_train_state()
-    if drop is not None:
-        enc.set_dropout(drop[0], drop[1], drop[2])
-    n = 4 * B
-    idd, mdd, tdd = ids_t.view(n, L).cuda(), mask_t.view(n, L).cuda(), types_t.view(n, L).cuda()
-    tdd = tdd if cfg.type_vocab_size else None
-    emb, _, saved = enc.forward(idd, mdd, tdd, training=True, precision=prec)
-    e4 = emb.view(4, B, -1)
-    S = 65536.0
-    loss, g = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2,
-                                  grad_out=torch.tensor([S], device="cuda"), want_grads=True)
-    enc.grads.zero_()
-    enc.backward(idd, mdd, tdd, stacked(g), saved, precision=prec)
-    torch.cuda.synchronize()
+    loss, emb, ga, _ = run_step(cfg, arena, ids_t, mask_t, types_t, B, L, precision=prec, scale=65536.0,
+                                setup=(lambda enc: enc.set_dropout(*drop)) if drop is not None else None)
     k = 1.0 / (1.0 - (drop[0] if drop is not None else 0.0))
     sc = max(1.0, float(emb32.detach().norm(dim=-1).mean()))                   # (bare bert-base emits un-normalised embeddings)
-    d = (emb.cpu().view(4, B, -1) - emb32.detach()).abs()
+    d = (emb - emb32.detach()).abs()
     atol = (1e-4 if prec == "f16w" else 2e-4) * k * sc
     bad = d > atol + 1e-3 * emb32.detach().abs()
-    print(f"[{prec} fwd] {name} B={B} L={L} drop={drop}: max|d emb| {float(d.max()):.2e} (atol {atol:.1e}), |d loss| {abs(loss.item() - loss32.item()):.1e}")
+    print(f"[{prec} fwd] {name} B={B} L={L} drop={drop}: max|d emb| {float(d.max()):.2e} (atol {atol:.1e}), |d loss| {abs(loss - loss32.item()):.1e}")
     assert not bool(bad.any()), (float(d.max()), atol, int(bad.sum()))
-    assert abs(loss.item() - loss32.item()) < 1e-3 * k * sc
+    assert abs(loss - loss32.item()) < 1e-3 * k * sc
     # a hinge within the forward tolerance of its kink is on in one implementation and off in the other (tests/test_gpu_fp8mx.py)
     eo = emb32.detach()
     dist = lambda x, y: (x - y + 1e-6).norm(dim=-1)                            # noqa: E731
@@ -496,7 +454,6 @@ def check_against_fp32_autograd(name, B, L, ragged, wkw, drop, prec, layers=None
         print(f"[{prec}] a hinge within {float(args.abs().min()):.1e} of its kink -- gradients not compared")
         return
     segs, _ = build_layout(cfg)
-    ga = enc.grads.cpu() / S
     assert torch.isfinite(ga).all()
     gnorm = float(torch.sqrt(sum((P[s_.name].grad.double() ** 2).sum() for s_ in segs)))
     cls_top = {}

@@ -12,28 +12,7 @@ pytestmark = pytest.mark.gpu
 import quadruplet_sentence_transformer_amd  # noqa: E402,F401
 from quadruplet_sentence_transformer_amd import _lib  # noqa: E402
 from oracle import torch_ref as R  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-def st():
-    return _lib.current_stream_ptr()
-
-
-def stage_major(s_rowmajor):
-    """[rows, K/32] scale bytes -> the library's layout [ceil(K/128)][rows][4] (zero-padded), flattened."""
-    rows, nb = s_rowmajor.shape
-    pad = (-nb) % 4
-    t = torch.nn.functional.pad(s_rowmajor, (0, pad))
-    return t.view(rows, (nb + pad) // 4, 4).permute(1, 0, 2).contiguous().view(-1)
-
-
-def row_major(s_stage, rows, K):
-    nb = K // 32
-    return s_stage.view((nb + 3) // 4, rows, 4).permute(1, 0, 2).reshape(rows, -1)[:, :nb]
+from kernel_helpers import gemm_args, lib, ln_epi, quad_batch, row_major, run_step, stage_major, stream  # noqa: E402,F401
 
 
 def quant_dev(lib, x, bf16=False):
@@ -41,7 +20,7 @@ def quant_dev(lib, x, bf16=False):
     src = x.cuda().to(torch.bfloat16 if bf16 else torch.float32).contiguous()
     q = torch.empty(rows, K, dtype=torch.uint8, device="cuda")
     s = torch.zeros((K + 127) // 128 * rows * 4, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.qst_quant_mx(src.data_ptr(), int(bf16), rows, K, q.data_ptr(), s.data_ptr(), st()))
+    _lib.check(lib.qst_quant_mx(src.data_ptr(), int(bf16), rows, K, q.data_ptr(), s.data_ptr(), stream()))
     return q, s
 
 
@@ -59,15 +38,7 @@ def test_mx_quantisation_is_bit_exact(lib, rows, K):
         q, s = quant_dev(lib, src, bf16)
         qr, sr, _ = R.mx_quant(src)
         assert torch.equal(s.cpu(), stage_major(sr)) and torch.equal(q.cpu(), qr)
-    assert lib.qst_quant_mx(x.cuda().data_ptr(), 0, rows, 48, q.data_ptr(), s.data_ptr(), st()) == -2     # K % 32
-
-
-def gemm_args(**kw):
-    a = _lib.QstGemmArgs()
-    a._keep = [v for v in kw.values() if torch.is_tensor(v)]
-    for k, v in kw.items():
-        setattr(a, k, v.data_ptr() if torch.is_tensor(v) else v)
-    return a
+    assert lib.qst_quant_mx(x.cuda().data_ptr(), 0, rows, 48, q.data_ptr(), s.data_ptr(), stream()) == -2     # K % 32
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 192, 128), (300, 384, 768), (1000, 2304, 768), (520, 768, 3072), (17000, 2304, 896)])
@@ -86,19 +57,19 @@ def test_gemm_f8_matches_fp32_on_dequantised_operands(lib, M, N, K):
     # fp32 out + bias + residual
     C = torch.empty(M, N, device="cuda")
     _lib.check(lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=C, bias=bias.cuda(), resid=resid.cuda(), M=M, N=N, K=K,
-                                            lda=K, ldb=K, ldc=N, ldr=N), 1, st()))
+                                            lda=K, ldb=K, ldc=N, ldr=N), 1, stream()))
     np.testing.assert_allclose(C.cpu().double().numpy(), (ref + bias.double() + resid.double()).numpy(), rtol=0, atol=2e-5 * acc_scale + 1e-5)
     # bf16 out + bias
     Cb = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
     _lib.check(lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=Cb, bias=bias.cuda(), M=M, N=N, K=K, lda=K, ldb=K, ldc=N),
-                                  0, st()))
+                                  0, stream()))
     np.testing.assert_allclose(Cb.float().cpu().double().numpy(), (ref + bias.double()).numpy(), rtol=8e-3, atol=8e-3 * scale)
     # gelu(acc + bias) as MXFP8
     if N % 128 == 0:
         Hq = torch.zeros(M, N, dtype=torch.uint8, device="cuda")
         Hs = torch.zeros(N // 128 * M * 4, dtype=torch.uint8, device="cuda")
         _lib.check(lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=Hq, C2=Hs, bias=bias.cuda(), M=M, N=N, K=K, lda=K, ldb=K,
-                                                ldc=N), 5, st()))
+                                                ldc=N), 5, stream()))
         h = torch.nn.functional.gelu((ref + bias.double()).float())
         qr, sr, dr = R.mx_quant(h)
         Hs = row_major(Hs.cpu(), M, N)
@@ -115,26 +86,26 @@ def test_gemm_f8_matches_fp32_on_dequantised_operands(lib, M, N, K):
     for tile in (0, 1):
         C8 = torch.empty(M, N, device="cuda")
         _lib.check(lib.qst_gemm_nt8_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=C8, bias=bias.cuda(), resid=resid.cuda(), M=M, N=N, K=K,
-                                                 lda=K, ldb=K, ldc=N, ldr=N), 1, tile, st()))
+                                                 lda=K, ldb=K, ldc=N, ldr=N), 1, tile, stream()))
         np.testing.assert_allclose(C8.cpu().double().numpy(), (ref + bias.double() + resid.double()).numpy(), rtol=0, atol=2e-5 * acc_scale + 1e-5)
         torch.testing.assert_close(C8, C, rtol=0, atol=2e-5 * acc_scale + 1e-5)
         Cb8 = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
         _lib.check(lib.qst_gemm_nt8_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=Cb8, bias=bias.cuda(), M=M, N=N, K=K, lda=K, ldb=K, ldc=N),
-                                       0, tile, st()))
+                                       0, tile, stream()))
         np.testing.assert_allclose(Cb8.float().cpu().double().numpy(), (ref + bias.double()).numpy(), rtol=8e-3, atol=8e-3 * scale)
         G1, H1 = torch.empty(M, N, dtype=torch.bfloat16, device="cuda"), torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
         G8, H8 = torch.empty_like(G1), torch.empty_like(H1)
         _lib.check(lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=G1, C2=H1, bias=bias.cuda(), M=M, N=N, K=K, lda=K, ldb=K,
-                                                ldc=N, splits=0x80), 2, st()))
+                                                ldc=N, splits=0x80), 2, stream()))
         _lib.check(lib.qst_gemm_nt8_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=G8, C2=H8, bias=bias.cuda(), M=M, N=N, K=K, lda=K, ldb=K,
-                                                 ldc=N), 2, tile, st()))
+                                                 ldc=N), 2, tile, stream()))
         torch.testing.assert_close(H8.float(), H1.float(), rtol=8e-3, atol=8e-3 * scale)
         torch.testing.assert_close(G8.float(), G1.float(), rtol=8e-3, atol=2e-2)
         if N % 128 == 0:
             # the training FFN-1 epilogue (gelu'(u), h as bf16 AND the bf16-rounded h as MXFP8): tiled against 8-phase, bit for bit
             # wherever the bf16 h agrees (the MX copy is a function of it)
             outs = []
-            for fn, extra in ((lib.qst_gemm_nt_f8, (6, st())), (lib.qst_gemm_nt8_f8, (6, tile, st()))):
+            for fn, extra in ((lib.qst_gemm_nt_f8, (6, stream())), (lib.qst_gemm_nt8_f8, (6, tile, stream()))):
                 Gm, Hm = torch.empty(M, N, dtype=torch.bfloat16, device="cuda"), torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
                 Qm = torch.zeros(M, N, dtype=torch.uint8, device="cuda")
                 Sm = torch.zeros(N // 128 * M * 4, dtype=torch.uint8, device="cuda")
@@ -150,8 +121,8 @@ def test_gemm_f8_matches_fp32_on_dequantised_operands(lib, M, N, K):
             assert same.float().mean().item() > 0.98
             assert torch.equal(Q6.view(M, N // 32, 32)[same], Q7.view(M, N // 32, 32)[same])
     # refused shapes
-    assert lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=C, M=M, N=N, K=K - 32, lda=K, ldb=K, ldc=N), 1, st()) == -2
-    assert lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, C=C, M=M, N=N, K=K, lda=K, ldb=K, ldc=N), 1, st()) == -1
+    assert lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=C, M=M, N=N, K=K - 32, lda=K, ldb=K, ldc=N), 1, stream()) == -2
+    assert lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, C=C, M=M, N=N, K=K, lda=K, ldb=K, ldc=N), 1, stream()) == -1
 
 
 def run_encoder_mx(name, B, L, weights_kw, layers=None, emb_atol=3e-3):
@@ -174,8 +145,7 @@ def run_encoder_mx(name, B, L, weights_kw, layers=None, emb_atol=3e-3):
         emb32 = R.st_head(tok32, mask_t, cfg.normalize)
     enc = HipEncoder(cfg)
     enc.load_arena(arena)
-    dev = [t.cuda() for t in (ids_t, mask_t, types_t)]
-    emb, tok, _ = enc.forward(dev[0], dev[1], dev[2] if cfg.type_vocab_size else None, want_tokens=True, precision="fp8")
+    emb, tok, _ = enc.forward(*quad_batch(cfg, ids_t, mask_t, types_t, B, L), want_tokens=True, precision="fp8")
     torch.cuda.synchronize()
     assert torch.isfinite(emb).all()
     sc = float(emb32.norm(dim=-1).mean())                  # bare bert-base has no Normalize module: scale the tolerance
@@ -227,15 +197,14 @@ def test_gemm_f8_with_fused_layernorm(lib, M, K, N):
                 torch.empty(M, N, dtype=torch.uint8, device="cuda"), torch.zeros(N // 128 * M * 4, dtype=torch.uint8, device="cuda"))
     s = torch.empty(M, N, device="cuda")
     _lib.check(lib.qst_gemm_nt_f8(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=s, bias=bias, resid=resid, M=M, N=N, K=K, lda=K, ldb=K,
-                                            ldc=N, ldr=N), 1, st()))
+                                            ldc=N, ldr=N), 1, stream()))
     y0, yb0, xh0, rs0, yq0, ys0 = outs()
     _lib.check(lib.qst_ln_fwd_mx_train(s.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-12, M, N, y0.data_ptr(), yb0.data_ptr(),
-                                       xh0.data_ptr(), rs0.data_ptr(), yq0.data_ptr(), ys0.data_ptr(), st()))
+                                       xh0.data_ptr(), rs0.data_ptr(), yq0.data_ptr(), ys0.data_ptr(), stream()))
     y1, yb1, xh1, rs1, yq1, ys1 = outs()
-    e = _lib.QstLnEpi()
-    e.gamma, e.beta, e.eps, e.xhat, e.rstd = gamma.data_ptr(), beta.data_ptr(), 1e-12, xh1.data_ptr(), rs1.data_ptr()
+    e = ln_epi(gamma=gamma, beta=beta, eps=1e-12, xhat=xh1, rstd=rs1)
     _lib.check(lib.qst_gemm_nt8_f8_ln(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=y1, C2=yb1, C3=yq1, C4=ys1, bias=bias, resid=resid,
-                                                M=M, N=N, K=K, lda=K, ldb=K, ldc=N, ldr=N), e, st()))
+                                                M=M, N=N, K=K, lda=K, ldb=K, ldc=N, ldr=N), e, stream()))
     torch.testing.assert_close(y1, y0, rtol=1e-4, atol=2e-4)
     torch.testing.assert_close(rs1, rs0, rtol=1e-4, atol=0)
     torch.testing.assert_close(yb1.float(), yb0.float(), rtol=8e-3, atol=1e-2)
@@ -244,10 +213,9 @@ def test_gemm_f8_with_fused_layernorm(lib, M, K, N):
     assert torch.equal(yq1.cpu(), qr) and torch.equal(ys1.cpu(), stage_major(sr))
     # inference: only y (f32) and its MXFP8 copy
     y2, _, _, _, yq2, ys2 = outs()
-    e2 = _lib.QstLnEpi()
-    e2.gamma, e2.beta, e2.eps = gamma.data_ptr(), beta.data_ptr(), 1e-12
+    e2 = ln_epi(gamma=gamma, beta=beta, eps=1e-12)
     _lib.check(lib.qst_gemm_nt8_f8_ln(gemm_args(A=Aq, B=Bq, aux=As, bscale=Bs, C=y2, C3=yq2, C4=ys2, bias=bias, resid=resid, M=M, N=N,
-                                                K=K, lda=K, ldb=K, ldc=N, ldr=N), e2, st()))
+                                                K=K, lda=K, ldb=K, ldc=N, ldr=N), e2, stream()))
     assert torch.equal(y2, y1) and torch.equal(yq2, yq1) and torch.equal(ys2, ys1)
     assert lib.qst_gemm_nt8_ln_timeouts() == 0
 
@@ -264,7 +232,7 @@ def test_layernorm_mx_output_equals_quantising_its_bf16_output(lib, M, H):
     yq = torch.empty(M, H, dtype=torch.uint8, device="cuda")
     ys = torch.zeros(H // 128 * M * 4, dtype=torch.uint8, device="cuda")
     _lib.check(lib.qst_ln_fwd_mx(s.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-12, M, H, y.data_ptr(), yb.data_ptr(),
-                                 yq.data_ptr(), ys.data_ptr(), st()))
+                                 yq.data_ptr(), ys.data_ptr(), stream()))
     ref = torch.nn.functional.layer_norm(s, (H,), gamma, beta, 1e-12)
     torch.testing.assert_close(y, ref, rtol=1e-5, atol=1e-5)
     qr, sr, _ = R.mx_quant(yb.float().cpu())
@@ -275,7 +243,7 @@ def test_layernorm_mx_output_equals_quantising_its_bf16_output(lib, M, H):
     pos = torch.arange(M, dtype=torch.int32).cuda() % 16
     word, pe = torch.randn(V, H, generator=g).cuda(), torch.randn(16, H, generator=g).cuda()
     _lib.check(lib.qst_embed_ln_fwd_mx(ids.data_ptr(), None, pos.data_ptr(), word.data_ptr(), pe.data_ptr(), None, gamma.data_ptr(),
-                                       beta.data_ptr(), 1e-12, M, H, y.data_ptr(), yb.data_ptr(), yq.data_ptr(), ys.data_ptr(), st()))
+                                       beta.data_ptr(), 1e-12, M, H, y.data_ptr(), yb.data_ptr(), yq.data_ptr(), ys.data_ptr(), stream()))
     ref = torch.nn.functional.layer_norm(word[ids] + pe[pos.long()], (H,), gamma, beta, 1e-12)
     torch.testing.assert_close(y, ref, rtol=1e-5, atol=1e-5)
     qr, sr, _ = R.mx_quant(yb.float().cpu())
@@ -320,7 +288,6 @@ def test_fp8_training_step_against_the_mx_oracle(name, B, L, layers, wkw, drop):
     of the e4m3 step)."""
     from dataclasses import replace
     from quadruplet_sentence_transformer_amd.config import PRESETS, build_layout
-    from quadruplet_sentence_transformer_amd.encoder import HipEncoder, quadruplet_loss_raw
     from quadruplet_sentence_transformer_amd.synthetic import synthetic_params, synthetic_quadruplets
     cfg = replace(PRESETS[name], num_layers=layers, vocab_size=4096)
     arena = synthetic_params(cfg, seed=14, **wkw)
@@ -339,32 +306,23 @@ def test_fp8_training_step_against_the_mx_oracle(name, B, L, layers, wkw, drop):
     loss_o = R.gamma_quadruplet_loss_ref(emb_o[0], emb_o[1], emb_o[2], emb_o[3], gamma=0.6, margin_pos_neg=1.0,
                                          margin_pos_part=0.5, margin_part_neg=0.5)
     loss_o.backward()
-    enc = HipEncoder(cfg)
-    enc.load_arena(arena)
-    enc.ensure_train_state()
-    if _LN_FUSION is not None:
-        enc.set_ln_fusion(_LN_FUSION)
-    if drop is not None:
-        enc.set_dropout(drop[0], drop[1], seed)
-    dev = [t.cuda() for t in (ids_t, mask_t, types_t)]
-    dt = dev[2] if cfg.type_vocab_size else None
-    emb, _, saved = enc.forward(dev[0], dev[1], dt, training=True, precision="fp8")
+    def setup(enc):
+        if _LN_FUSION is not None:
+            enc.set_ln_fusion(_LN_FUSION)
+        if drop is not None:
+            enc.set_dropout(drop[0], drop[1], seed)
+    loss, emb, ga, enc = run_step(cfg, arena, ids_t, mask_t, types_t, B, L, precision="fp8", setup=setup)
     if drop is not None:
         assert enc.dropout_step == 1 and enc.drop_state.cpu().tolist()[2] == 1
-    e4 = emb.view(4, B, -1)
-    loss, g = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2, want_grads=True)
-    enc.grads.zero_()
-    enc.backward(dev[0], dev[1], dt, torch.cat(g, 0), saved, precision="fp8")
-    torch.cuda.synchronize()
     # the training forward computes what the inference forward computes
-    emb_inf, _, _ = enc.forward(dev[0], dev[1], dt, precision="fp8")
+    emb_inf = enc.forward(*quad_batch(cfg, ids_t, mask_t, types_t, B, L), precision="fp8")[0].cpu().view(4, B, -1)
     sc = float(emb_o.detach().norm(dim=-1).mean())
     if drop is None:
         assert float((emb - emb_inf).abs().max()) / sc < 4e-3
     else:
         assert float((emb - emb_inf).abs().max()) / sc > 5e-3            # (the masks did something: more than the parity bar)
-    e_err = float((emb.cpu().view(4, B, -1) - emb_o.detach()).abs().max()) / sc
-    l_err = abs(loss.item() - loss_o.item()) / max(1.0, sc)                # (bare bert-base emits un-normalised embeddings)
+    e_err = float((emb - emb_o.detach()).abs().max()) / sc
+    l_err = abs(loss - loss_o.item()) / max(1.0, sc)                       # (bare bert-base emits un-normalised embeddings)
     print(f"[fp8-train fwd] {name} drop={drop}: embeddings {e_err:.2e}, loss {l_err:.2e}")
     # 4e-3 is the dropout-free bar (this suite's maximum without dropout is 3.1e-3: mpnet dims, 2 layers, 5 x 32 tokens). In train()
     # mode every kept activation -- and with it every absolute rounding difference between two implementations of the same
@@ -376,7 +334,6 @@ def test_fp8_training_step_against_the_mx_oracle(name, B, L, layers, wkw, drop):
     e_bar = 4e-3 / (1.0 - (drop[0] if drop is not None else 0.0))
     assert e_err < e_bar and l_err < 5e-3, (e_err, e_bar, l_err)
     segs, _ = build_layout(cfg)
-    ga = enc.grads.cpu()
     assert torch.isfinite(ga).all()
     # The loss is a sum of hinges: a hinge whose argument sits within the forward tolerance of zero is on in one implementation
     # and off in the other, and its whole gradient comes or goes (loss equal to 7e-5, gradients 0.68 apart on a one-quadruplet

@@ -14,6 +14,7 @@ from quadruplet_sentence_transformer_amd.encoder import HipEncoder, quadruplet_l
 from quadruplet_sentence_transformer_amd.losses import GammaQuadrupletLoss, gamma_quadruplet_loss  # noqa: E402
 from quadruplet_sentence_transformer_amd.synthetic import approx_normal, synthetic_params, synthetic_quadruplets  # noqa: E402
 from tests.test_oracle_golden import CLI, CLS, ENC_CASES, LOSS_CASES, golden_inputs, loss_inputs  # noqa: E402
+from kernel_helpers import quad_batch, run_step  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -65,27 +66,16 @@ def test_hip_encoder_matches_hf_vectors(enc_g, key, preset, B, L, wkw, store):
     cfg = PRESETS[preset]
     arena = synthetic_params(cfg, seed=14, **wkw)
     ids, mask, types = golden_inputs(key, cfg, B, L)
-    enc = HipEncoder(cfg)
-    enc.load_arena(arena)
-    n = 4 * B
-    idd = torch.from_numpy(ids).view(n, L).cuda()
-    mdd = torch.from_numpy(mask).view(n, L).cuda()
-    tdd = torch.from_numpy(types).view(n, L).cuda() if cfg.type_vocab_size else None
-    emb, _, saved = enc.forward(idd, mdd, tdd, training=True)
-    e4 = emb.view(4, B, -1)
-    loss, g = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2, want_grads=True)
+    loss, e4, ga, _ = run_step(cfg, arena, ids, mask, types, B, L)
+    ga = ga.numpy()
     # the two 12-layer full-dims cases (round 5): twice the depth, twice the accumulated operand rounding -- bf16 measured
     # 3.1e-3 / 1.1e-2 on the loss and 1.7e-3 / 3.8e-2 on the embeddings (bert-base: no Normalize module, magnitudes ~1);
     # tools/f16_gpu_report.py prints every precision's distance on every case
     loss_tol, emb_tol = {"mpnetbase_trained": (6e-3, 3e-3), "bertbase_trained": (2e-2, 6e-2)}.get(key, (1e-3, 2e-3))
-    assert abs(loss.item() - float(enc_g[key + "_loss"])) < loss_tol
-    np.testing.assert_allclose(e4.cpu().numpy(), enc_g[key + "_emb"], rtol=0, atol=emb_tol)
+    assert abs(loss - float(enc_g[key + "_loss"])) < loss_tol
+    np.testing.assert_allclose(e4.numpy(), enc_g[key + "_emb"], rtol=0, atol=emb_tol)
     if key.endswith("maskedge"):
         assert (e4[0, 1] == 0).all()                     # the all-padding sequence: exactly HF + ST's zero embedding
-    enc.ensure_train_state()
-    enc.grads.zero_()
-    enc.backward(idd, mdd, tdd, torch.cat(g, 0), saved)
-    ga = enc.grads.cpu().numpy()
     assert np.isfinite(ga).all()
     segs, _ = build_layout(cfg)
     if store == "full":
@@ -121,10 +111,7 @@ def test_hip_parity_precision_matches_hf_vectors(enc_g, key, preset, B, L, wkw, 
     enc = HipEncoder(cfg)
     enc.load_arena(arena)
     n = 4 * B
-    idd = torch.from_numpy(ids).view(n, L).cuda()
-    mdd = torch.from_numpy(mask).view(n, L).cuda()
-    tdd = torch.from_numpy(types).view(n, L).cuda() if cfg.type_vocab_size else None
-    emb, tok, _ = enc.forward(idd, mdd, tdd, training=False, want_tokens=True, precision="bf16x3")
+    emb, tok, _ = enc.forward(*quad_batch(cfg, ids, mask, types, B, L), training=False, want_tokens=True, precision="bf16x3")
     e4 = emb.view(4, B, -1)
     np.testing.assert_allclose(e4.cpu().numpy(), enc_g[key + "_emb"], rtol=1e-3, atol=1e-4)
     loss, _ = quadruplet_loss_raw(e4[0], e4[1], e4[2], e4[3], 0.6, 1.0, 0.5, 0.5, 2.0, False, 2)

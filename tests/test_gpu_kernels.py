@@ -19,43 +19,20 @@ import quadruplet_sentence_transformer_amd as qst  # noqa: E402
 from quadruplet_sentence_transformer_amd import _lib  # noqa: E402
 from quadruplet_sentence_transformer_amd.encoder import quadruplet_loss_raw  # noqa: E402
 from oracle import torch_ref as R  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
+from kernel_helpers import (OPDT, attn_desc, attn_ref, ffn_args, gemm_args, kf, ln_epi, lib, op, opr,  # noqa: E402,F401
+                            stream)
 
 
 def dev(t):
     return t.cuda().contiguous()
 
 
-def stream():
-    return _lib.current_stream_ptr()
+def f32(*shape):
+    return torch.empty(*shape, dtype=torch.float32, device="cuda")
 
 
-def bfr(t):
-    return t.to(torch.bfloat16).to(torch.float32)
-
-
-# The kernels with 16-bit matrix-core operands exist on bf16 (qst_*) and on IEEE half (qst_*_f16: QST_PREC_F16, the same
-# sources compiled on the other operand type); their tests run on both.
-OPDT = {"bf16": torch.bfloat16, "f16": torch.float16}
-
-
-@pytest.fixture(params=["bf16", "f16"])
-def op(request):
-    return request.param
-
-
-def opr(op, t):
-    """t rounded to the operand type and back (what the kernel's operand holds)."""
-    return t.to(OPDT[op]).to(torch.float32)
-
-
-def kf(lib, name, op):
-    return _lib.kfn(lib, name, op)
+def b16(op, *shape):
+    return torch.empty(*shape, dtype=OPDT[op], device="cuda")
 
 
 # ------------------------------------------------------------------ loss
@@ -113,14 +90,6 @@ def test_loss_bad_args(lib):
 
 
 # ------------------------------------------------------------------ GEMM
-def gemm_args(**kw):
-    g = _lib.QstGemmArgs()
-    g._keep = [v for v in kw.values() if torch.is_tensor(v)]   # keep device tensors alive until the launch is enqueued
-    for k, v in kw.items():
-        setattr(g, k, v.data_ptr() if torch.is_tensor(v) else v)
-    return g
-
-
 @pytest.mark.parametrize("form", [0, 2, 4, 0x20, 0x40], ids=["tiles128", "tiles256", "tall256", "eightphase128x384", "eightphase256x256"])
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 384), (200, 192, 128), (1000, 1152, 384), (64, 64, 64),
                                    (4096, 384, 1536), (5000, 1536, 384), (20000, 1152, 384), (12000, 768, 768),
@@ -352,26 +321,13 @@ def test_gemm_nt8_ln_direct(lib, op, M, K, N):
     gamma, beta = dev(1 + 0.1 * torch.randn(N, generator=g)), dev(0.1 * torch.randn(N, generator=g))
     eps = 1e-12
 
-    def ln_epi(**kw):
-        e = _lib.QstLnEpi()
-        e._keep = [v for v in kw.values() if torch.is_tensor(v)]
-        for k, v in kw.items():
-            setattr(e, k, v.data_ptr() if torch.is_tensor(v) else v)
-        return e
-
-    def f32(*shape):
-        return torch.empty(*shape, dtype=torch.float32, device="cuda")
-
-    def b16(*shape):
-        return torch.empty(*shape, dtype=OPDT[op], device="cuda")
-
     base = dict(A=Ad, B=Bd, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, ldr=N)
     s = f32(M, N)
     _lib.check(kf(lib, "qst_gemm_nt", op)(gemm_args(**base, C=s, bias=bias, resid=resid), 1, stream()))
-    y0, yb0, xh0, rs0 = f32(M, N), b16(M, N), b16(M, N), f32(M)
+    y0, yb0, xh0, rs0 = f32(M, N), b16(op, M, N), b16(op, M, N), f32(M)
     _lib.check(kf(lib, "qst_ln_fwd", op)(s.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, M, N, y0.data_ptr(), yb0.data_ptr(),
                               xh0.data_ptr(), rs0.data_ptr(), stream()))
-    y1, yb1, xh1, rs1 = f32(M, N), b16(M, N), b16(M, N), f32(M)
+    y1, yb1, xh1, rs1 = f32(M, N), b16(op, M, N), b16(op, M, N), f32(M)
     _lib.check(kf(lib, "qst_gemm_nt8_ln", op)(gemm_args(**base, C=y1, C2=yb1, bias=bias, resid=resid),
                                    ln_epi(gamma=gamma, beta=beta, eps=eps, xhat=xh1, rstd=rs1), 0, stream()))
     torch.testing.assert_close(y1, y0, rtol=1e-4, atol=1e-4)
@@ -380,14 +336,14 @@ def test_gemm_nt8_ln_direct(lib, op, M, K, N):
     torch.testing.assert_close(xh1.float(), xh0.float(), rtol=8e-3, atol=1e-2)
     dy = f32(M, N)
     _lib.check(kf(lib, "qst_gemm_nt", op)(gemm_args(**base, C=dy, resid=resid), 1, stream()))
-    ds0, dsb0 = f32(M, N), b16(M, N)
+    ds0, dsb0 = f32(M, N), b16(op, M, N)
     dg0, db0 = torch.zeros(N, device="cuda"), torch.zeros(N, device="cuda")
     scratch = torch.empty(lib.qst_ln_bwd_scratch_bytes(M, N) // 4, device="cuda")
     _lib.check(kf(lib, "qst_ln_bwd", op)(dy.data_ptr(), xh0.data_ptr(), rs0.data_ptr(), gamma.data_ptr(), M, N, ds0.data_ptr(),
                               dsb0.data_ptr(), dg0.data_ptr(), db0.data_ptr(), scratch.data_ptr(), stream()))
     br = kf(lib, "qst_gemm_nt8_ln_block_rows", op)(M, N)
     part = torch.full(((M + br - 1) // br, 2, N), float("nan"), device="cuda")
-    ds1, dsb1 = f32(M, N), b16(M, N)
+    ds1, dsb1 = f32(M, N), b16(op, M, N)
     _lib.check(kf(lib, "qst_gemm_nt8_ln", op)(gemm_args(**base, C=ds1, C2=dsb1, resid=resid),
                                    ln_epi(gamma=gamma, xhat=xh0, rstd=rs0, partials=part), 1, stream()))
     scale = ds0.abs().max().item()
@@ -443,27 +399,14 @@ def test_gemm_nt_fused_layernorm(lib, op, M, K, N):
     gamma, beta = dev(1 + 0.1 * torch.randn(N, generator=g)), dev(0.1 * torch.randn(N, generator=g))
     eps = 1e-12
 
-    def ln_epi(**kw):
-        e = _lib.QstLnEpi()
-        e._keep = [v for v in kw.values() if torch.is_tensor(v)]
-        for k, v in kw.items():
-            setattr(e, k, v.data_ptr() if torch.is_tensor(v) else v)
-        return e
-
-    def f32(*shape):
-        return torch.empty(*shape, dtype=torch.float32, device="cuda")
-
-    def b16(*shape):
-        return torch.empty(*shape, dtype=OPDT[op], device="cuda")
-
     # ---- forward: y = LN(A.B^T + bias + resid)
     s = f32(M, N)
     _lib.check(kf(lib, "qst_gemm_nt", op)(gemm_args(A=Ad, B=Bd, C=s, bias=bias, resid=resid, M=M, N=N, K=K, lda=K, ldb=K, ldc=N,
                                          ldr=N), 1, stream()))
-    y0, yb0, xh0, rs0 = f32(M, N), b16(M, N), b16(M, N), f32(M)
+    y0, yb0, xh0, rs0 = f32(M, N), b16(op, M, N), b16(op, M, N), f32(M)
     _lib.check(kf(lib, "qst_ln_fwd", op)(s.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, M, N, y0.data_ptr(), yb0.data_ptr(),
                               xh0.data_ptr(), rs0.data_ptr(), stream()))
-    y1, yb1, xh1, rs1 = f32(M, N), b16(M, N), b16(M, N), f32(M)
+    y1, yb1, xh1, rs1 = f32(M, N), b16(op, M, N), b16(op, M, N), f32(M)
     _lib.check(kf(lib, "qst_gemm_nt_ln", op)(gemm_args(A=Ad, B=Bd, C=y1, C2=yb1, bias=bias, resid=resid, M=M, N=N, K=K, lda=K, ldb=K,
                                             ldc=N, ldr=N),
                                   ln_epi(gamma=gamma, beta=beta, eps=eps, xhat=xh1, rstd=rs1), 0, stream()))
@@ -483,12 +426,12 @@ def test_gemm_nt_fused_layernorm(lib, op, M, K, N):
     dy = f32(M, N)
     _lib.check(kf(lib, "qst_gemm_nt", op)(gemm_args(A=Ad, B=Bd, C=dy, resid=resid, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, ldr=N), 1,
                                stream()))
-    ds0, dsb0 = f32(M, N), b16(M, N)
+    ds0, dsb0 = f32(M, N), b16(op, M, N)
     dg0, db0 = torch.zeros(N, device="cuda"), torch.zeros(N, device="cuda")
     scratch = torch.empty(lib.qst_ln_bwd_scratch_bytes(M, N) // 4, device="cuda")
     _lib.check(kf(lib, "qst_ln_bwd", op)(dy.data_ptr(), xh0.data_ptr(), rs0.data_ptr(), gamma.data_ptr(), M, N, ds0.data_ptr(),
                               dsb0.data_ptr(), dg0.data_ptr(), db0.data_ptr(), scratch.data_ptr(), stream()))
-    ds1, dsb1 = f32(M, N), b16(M, N)
+    ds1, dsb1 = f32(M, N), b16(op, M, N)
     br = lib.qst_gemm_nt_ln_block_rows_m(N, M)
     ntile = (M + br - 1) // br
     part = torch.full((ntile, 2, N), float("nan"), device="cuda")
@@ -516,8 +459,7 @@ def test_gemm_nt_fused_layernorm_n768_under_graph_capture(lib):
     bias, resid = dev(torch.randn(N, generator=g)), dev(torch.randn(M, N, generator=g))
     gamma, beta = dev(1 + 0.1 * torch.randn(N, generator=g)), dev(0.1 * torch.randn(N, generator=g))
     y0, y1 = torch.empty(M, N, device="cuda"), torch.empty(M, N, device="cuda")
-    e = _lib.QstLnEpi()
-    e.gamma, e.beta, e.eps = gamma.data_ptr(), beta.data_ptr(), 1e-12
+    e = ln_epi(gamma=gamma, beta=beta, eps=1e-12)
 
     def launch(out):
         _lib.check(lib.qst_gemm_nt_ln(gemm_args(A=A, B=B, C=out, bias=bias, resid=resid, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, ldr=N),
@@ -558,36 +500,16 @@ def test_ffn_chain_matches_the_two_kernel_path(lib, op, M, I):
     gamma, beta = dev(1 + 0.1 * torch.randn(H, generator=g)), dev(0.1 * torch.randn(H, generator=g))
     eps = 1e-12
 
-    def ln_epi(**kw):
-        e = _lib.QstLnEpi()
-        e._keep = [v for v in kw.values() if torch.is_tensor(v)]
-        for k, v in kw.items():
-            setattr(e, k, v.data_ptr() if torch.is_tensor(v) else v)
-        return e
-
-    def ffn_args(**kw):
-        a = _lib.QstFfnArgs()
-        a._keep = [v for v in kw.values() if torch.is_tensor(v)]
-        for k, v in kw.items():
-            setattr(a, k, v.data_ptr() if torch.is_tensor(v) else v)
-        return a
-
-    def f32(*shape):
-        return torch.empty(*shape, dtype=torch.float32, device="cuda")
-
-    def b16(*shape):
-        return torch.empty(*shape, dtype=bf, device="cuda")
-
     # ---- forward, two kernels
-    gp0, h0 = b16(M, I), b16(M, I)
+    gp0, h0 = b16(op, M, I), b16(op, M, I)
     _lib.check(kf(lib, "qst_gemm_nt", op)(gemm_args(A=A, B=W1, C=gp0, C2=h0, bias=b1, M=M, N=I, K=H, lda=H, ldb=H, ldc=I), 2, stream()))
-    y0, yb0, xh0, rs0 = f32(M, H), b16(M, H), b16(M, H), f32(M)
+    y0, yb0, xh0, rs0 = f32(M, H), b16(op, M, H), b16(op, M, H), f32(M)
     _lib.check(kf(lib, "qst_gemm_nt_ln", op)(gemm_args(A=h0, B=W2, C=y0, C2=yb0, bias=b2, resid=resid, M=M, N=H, K=I, lda=I, ldb=I,
                                             ldc=H, ldr=H), ln_epi(gamma=gamma, beta=beta, eps=eps, xhat=xh0, rstd=rs0), 0,
                                   stream()))
     # ---- forward, one kernel (training: side outputs; inference: none)
     gp1, h1 = torch.full((M, I), 7.0, dtype=bf, device="cuda"), torch.full((M, I), 7.0, dtype=bf, device="cuda")
-    y1, yb1, xh1, rs1 = f32(M, H), b16(M, H), b16(M, H), f32(M)
+    y1, yb1, xh1, rs1 = f32(M, H), b16(op, M, H), b16(op, M, H), f32(M)
     _lib.check(kf(lib, "qst_ffn_chain", op)(ffn_args(A=A, B1=W1, B2=W2, bias1=b1, bias2=b2, resid=resid, save_gp=gp1, save_h=h1, C=y1,
                                           C2=yb1, M=M, H=H, I=I),
                                  ln_epi(gamma=gamma, beta=beta, eps=eps, xhat=xh1, rstd=rs1), 0, stream()))
@@ -611,14 +533,14 @@ def test_ffn_chain_matches_the_two_kernel_path(lib, op, M, I):
     # ---- backward: du = (ds2 . W2) * gelu'(u) ; ds1 = LN1'(du . W1 + ds2)
     ds2 = dev(torch.randn(M, H, generator=g))
     ds2b = ds2.to(bf)
-    du0 = b16(M, I)
+    du0 = b16(op, M, I)
     _lib.check(kf(lib, "qst_gemm_nt", op)(gemm_args(A=ds2b, B=W2t, C=du0, aux=gp0, M=M, N=I, K=H, lda=H, ldb=H, ldc=I), 3, stream()))
     ntile = (M + 127) // 128
-    o0, ob0, part0 = f32(M, H), b16(M, H), f32(ntile, 2, H)
+    o0, ob0, part0 = f32(M, H), b16(op, M, H), f32(ntile, 2, H)
     _lib.check(kf(lib, "qst_gemm_nt_ln", op)(gemm_args(A=du0, B=W1t, C=o0, C2=ob0, resid=ds2, M=M, N=H, K=I, lda=I, ldb=I, ldc=H, ldr=H),
                                   ln_epi(gamma=gamma, xhat=xh0, rstd=rs0, partials=part0), 1, stream()))
     du1 = torch.full((M, I), 7.0, dtype=bf, device="cuda")
-    o1, ob1, part1 = f32(M, H), b16(M, H), torch.full((ntile, 2, H), float("nan"), device="cuda")
+    o1, ob1, part1 = f32(M, H), b16(op, M, H), torch.full((ntile, 2, H), float("nan"), device="cuda")
     _lib.check(kf(lib, "qst_ffn_chain", op)(ffn_args(A=ds2b, B1=W2t, B2=W1t, resid=ds2, aux=gp0, save_h=du1, C=o1, C2=ob1, M=M, H=H, I=I),
                                  ln_epi(gamma=gamma, xhat=xh0, rstd=rs0, partials=part1), 1, stream()))
     torch.cuda.synchronize()
@@ -635,17 +557,6 @@ def test_ffn_chain_matches_the_two_kernel_path(lib, op, M, I):
 
 
 # ------------------------------------------------------------------ attention
-def attn_ref(qkv, mask, rel, n, L, A, d):
-    H = A * d
-    q, k, v = [t.view(n, L, A, d).transpose(1, 2) for t in qkv.view(n, L, 3 * H).split(H, dim=-1)]
-    s = q @ k.transpose(-1, -2) / math.sqrt(d)
-    if rel is not None:
-        s = s + rel[None]
-    s = s + (1.0 - mask[:, None, None, :].float()) * torch.finfo(torch.float32).min
-    p = torch.softmax(s, -1)
-    return (p @ v).transpose(1, 2).reshape(n * L, H)
-
-
 @pytest.mark.parametrize("n,L,A,d,use_rel", [(2, 32, 2, 32, False), (3, 128, 12, 32, False), (2, 160, 2, 64, True),
                                               (2, 256, 3, 64, False), (1, 384, 2, 64, True), (2, 64, 2, 32, True),
                                               (5, 96, 3, 32, False), (2, 160, 2, 32, True), (2, 512, 2, 64, False),
@@ -696,11 +607,9 @@ def test_attention_fwd_bwd(lib, op, n, L, A, d, use_rel):
         # must agree with it
         dq2 = torch.empty_like(dq)
         drel2 = torch.zeros(A, 2 * L, device="cuda") if use_rel else None
-        q = _lib.QstAttnDesc()
-        q.qkv, q.mask, q.rel_pos, q.nseq, q.L, q.A, q.d = qd.data_ptr(), md.data_ptr(), _lib.ptr(reld), n, L, A, d
-        q.ctx, q.lse, q.dctx, q.dqkv, q.drel = ctx.data_ptr(), lse.data_ptr(), dcd.data_ptr(), dq2.data_ptr(), _lib.ptr(drel2)
         # force_split = 1: the two-kernel path (the first call above ran the one-workgroup kernel where there is one)
-        q.delta_scratch, q.force_split = delta.data_ptr(), 1
+        q = attn_desc(qkv=qd, mask=md, rel_pos=reld, nseq=n, L=L, A=A, d=d, ctx=ctx, lse=lse, dctx=dcd, dqkv=dq2, drel=drel2,
+                      delta_scratch=delta, force_split=1)
         _lib.check(kf(lib, "qst_attention_bwd_ex", op)(q, stream()))
         torch.cuda.synchronize()
         torch.testing.assert_close(dq.float(), dq2.float(), rtol=2e-2, atol=2e-2 * max(1.0, gref.abs().max().item()))
@@ -756,12 +665,7 @@ def test_attention_bwd_x3_matches_the_fp32_kernel_and_autograd(lib, n, L, A, d, 
     if not drop:
         qr = qkv.double().requires_grad_(True)
         relr = rel.double().requires_grad_(True) if use_rel else None
-        q, k, v = [t.view(n, L, A, d).transpose(1, 2) for t in qr.view(n, L, 3 * H).split(H, dim=-1)]
-        sc = q @ k.transpose(-1, -2) / math.sqrt(d)
-        if use_rel:
-            sc = sc + relr[None]
-        sc = sc + (1.0 - mask[:, None, None, :].double()) * torch.finfo(torch.float32).min
-        ref = (torch.softmax(sc, -1) @ v).transpose(1, 2).reshape(n * L, H)
+        ref = attn_ref(qr, mask, relr, n, L, A, d)
         (ref * dctx.double()).sum().backward()
         torch.testing.assert_close(out["x3"][0].double(), qr.grad, rtol=1e-4, atol=2e-5 * max(1.0, scale))
         if use_rel:

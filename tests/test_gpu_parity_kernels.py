@@ -13,32 +13,11 @@ pytestmark = pytest.mark.gpu
 import quadruplet_sentence_transformer_amd  # noqa: E402,F401
 from quadruplet_sentence_transformer_amd import _lib  # noqa: E402
 from oracle import dropout_ref as D  # noqa: E402
-from test_gpu_row_kernels import embed_inputs, embed_sum_ref, drop_state, drop_desc  # noqa: E402
+from kernel_helpers import attn_ref, drop_desc, drop_state, gemm_args, lib, ptr, stream  # noqa: E402,F401
+from test_gpu_row_kernels import embed_inputs, embed_sum_ref  # noqa: E402
 
 BAD_ARG, UNSUPPORTED = -1, -2
 SQRT1_2 = 1.0 / math.sqrt(2.0)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-def stream():
-    return _lib.current_stream_ptr()
-
-
-def p(t):
-    return None if t is None else t.data_ptr()
-
-
-def gemm_args(**kw):
-    g = _lib.QstGemmArgs()
-    g._keep = [v for v in kw.values() if torch.is_tensor(v)]
-    for k, v in kw.items():
-        setattr(g, k, v.data_ptr() if torch.is_tensor(v) else v)
-    return g
 
 
 def gelu64(x):
@@ -199,7 +178,7 @@ def test_embed_sum_f32_is_exact(lib, M, H):
         x = embed_inputs(M, H, g, types=types)
         d = {k: (v.cuda() if v is not None else None) for k, v in x.items()}
         s = torch.full((M, H), float("nan"), device="cuda")
-        _lib.check(lib.qst_embed_sum_f32(p(d["ids"]), p(d["tid"]), p(d["pos"]), p(d["word"]), p(d["pe"]), p(d["te"]), M, H,
+        _lib.check(lib.qst_embed_sum_f32(ptr(d["ids"]), ptr(d["tid"]), ptr(d["pos"]), ptr(d["word"]), ptr(d["pe"]), ptr(d["te"]), M, H,
                                          s.data_ptr(), stream()))
         assert torch.equal(s.cpu(), embed_sum_ref(x)), types
 
@@ -239,17 +218,6 @@ def test_ln_bwd_f32_matches_fp64_autograd(lib, M, H):
 
 
 # ------------------------------------------------------------------ attention
-def attn_ref64(qkv, mask, rel, n, L, A, d):
-    """fp64 HF attention (modeling_bert.py BertSelfAttention; MPNet adds the position bias before the mask)"""
-    H = A * d
-    q, k, v = [t.view(n, L, A, d).transpose(1, 2) for t in qkv.view(n, L, 3 * H).split(H, dim=-1)]
-    sc = q @ k.transpose(-1, -2) / math.sqrt(d)
-    if rel is not None:
-        sc = sc + rel[None]
-    sc = sc + (1.0 - mask[:, None, None, :].double()) * torch.finfo(torch.float32).min
-    return (torch.softmax(sc, -1) @ v).transpose(1, 2).reshape(n * L, H)
-
-
 def attn_case(n, L, A, d, use_rel, seed):
     g = torch.Generator().manual_seed(seed)
     H = A * d
@@ -262,7 +230,7 @@ def attn_case(n, L, A, d, use_rel, seed):
     dctx = torch.randn(n * L, H, generator=g)
     qr = qkv.double().requires_grad_(True)
     relr = rel.double().requires_grad_(True) if use_rel else None
-    ref = attn_ref64(qr, mask, relr, n, L, A, d)
+    ref = attn_ref(qr, mask, relr, n, L, A, d)
     (ref * dctx.double()).sum().backward()
     return qkv, mask, rel, dctx, ref.detach(), qr.grad, (relr.grad if use_rel else None)
 
@@ -272,8 +240,8 @@ def run_attn_bwd_f32(lib, qkv, ctx, dctx, mask, rel, n, L, A, d):
     qd, cd, dcd, md, reld = qkv.cuda(), ctx.cuda(), dctx.cuda(), mask.cuda(), (rel.cuda() if rel is not None else None)
     dq = torch.full((n * L, 3 * H), float("nan"), device="cuda")
     drel = torch.zeros(A, L, L, device="cuda") if rel is not None else None
-    _lib.check(lib.qst_attention_bwd_f32(qd.data_ptr(), cd.data_ptr(), dcd.data_ptr(), md.data_ptr(), p(reld), n, L, A, d,
-                                         dq.data_ptr(), p(drel), stream()))
+    _lib.check(lib.qst_attention_bwd_f32(qd.data_ptr(), cd.data_ptr(), dcd.data_ptr(), md.data_ptr(), ptr(reld), n, L, A, d,
+                                         dq.data_ptr(), ptr(drel), stream()))
     torch.cuda.synchronize()
     return dq.cpu(), (drel.cpu() if rel is not None else None)
 
@@ -295,7 +263,7 @@ def test_attention_x3_forward_and_fp32_backward_match_fp64(lib, L, d, use_rel):
     qkv, mask, rel, dctx, ref, gq, grel = attn_case(n, L, A, d, use_rel, 13 * L + d + int(use_rel))
     qd, md, reld = qkv.cuda(), mask.cuda(), (rel.cuda() if use_rel else None)
     ctx = torch.full((n * L, A * d), float("nan"), device="cuda")
-    _lib.check(lib.qst_attention_fwd_x3(qd.data_ptr(), md.data_ptr(), p(reld), n, L, A, d, ctx.data_ptr(), stream()))
+    _lib.check(lib.qst_attention_fwd_x3(qd.data_ptr(), md.data_ptr(), ptr(reld), n, L, A, d, ctx.data_ptr(), stream()))
     ctx_c = ctx.cpu()
     torch.testing.assert_close(ctx_c.double(), ref, rtol=1e-4, atol=2e-5 * max(1.0, ref.abs().max().item()))
     dq, drel = run_attn_bwd_f32(lib, qkv, ctx_c, dctx, mask, rel, n, L, A, d)
@@ -328,10 +296,10 @@ def test_dropout_apply_f32_matches_the_oracle_mask(lib, n):
     for resid in (None, rd):
         want = x * mk + (r if resid is not None else 0.0)
         out = torch.full((n,), float("nan"), device="cuda")
-        _lib.check(lib.qst_dropout_apply_f32(C.byref(dd), xd.data_ptr(), p(resid), n, out.data_ptr(), stream()))
+        _lib.check(lib.qst_dropout_apply_f32(C.byref(dd), xd.data_ptr(), ptr(resid), n, out.data_ptr(), stream()))
         assert torch.equal(out.cpu(), want)
         inplace = xd.clone()
-        _lib.check(lib.qst_dropout_apply_f32(C.byref(dd), inplace.data_ptr(), p(resid), n, inplace.data_ptr(), stream()))
+        _lib.check(lib.qst_dropout_apply_f32(C.byref(dd), inplace.data_ptr(), ptr(resid), n, inplace.data_ptr(), stream()))
         assert torch.equal(inplace.cpu(), want)
     assert lib.qst_dropout_apply_f32(C.byref(dd), xd.data_ptr(), None, n - 2 if n > 4 else 6, xd.data_ptr(), stream()) == BAD_ARG
     assert lib.qst_dropout_apply_f32(None, xd.data_ptr(), None, n, xd.data_ptr(), stream()) == BAD_ARG

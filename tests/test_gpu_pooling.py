@@ -17,6 +17,7 @@ from quadruplet_sentence_transformer_amd.encoder import HipEncoder
 from quadruplet_sentence_transformer_amd.synthetic import synthetic_params, synthetic_quadruplets
 from quadruplet_sentence_transformer_amd.trainer import QuadrupletTrainer, warmup_linear_lr
 from oracle import torch_ref as R
+from kernel_helpers import lib, quad_batch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -52,8 +53,7 @@ def ragged_mask(n, L, gen):
     return (torch.arange(L)[None, :] < lens[:, None]).to(torch.int64)
 
 
-def pool_fwd(tok, mask, mode, normalize, H):
-    lib = _lib.load()
+def pool_fwd(lib, tok, mask, mode, normalize, H):
     n, L, _ = tok.shape
     D = bin(mode).count("1") * H
     emb = torch.full((n, D), float("nan"), device="cuda")
@@ -64,8 +64,7 @@ def pool_fwd(tok, mask, mode, normalize, H):
     return emb, pooled, argmax
 
 
-def pool_bwd(demb, pooled, argmax, mask, mode, normalize, L, H):
-    lib = _lib.load()
+def pool_bwd(lib, demb, pooled, argmax, mask, mode, normalize, L, H):
     n = demb.shape[0]
     dtok = torch.full((n, L, H), float("nan"), device="cuda")
     _lib.check(lib.qst_pool_bwd(demb.data_ptr(), pooled.data_ptr(), argmax.data_ptr(), mask.data_ptr(), n, L, H, mode, int(normalize),
@@ -75,7 +74,7 @@ def pool_bwd(demb, pooled, argmax, mask, mode, normalize, L, H):
 
 @pytest.mark.parametrize("normalize", [False, True])
 @pytest.mark.parametrize("pooling", HEADS)
-def test_pool_kernels_match_torch(pooling, normalize):
+def test_pool_kernels_match_torch(lib, pooling, normalize):
     mode = pooling_mask(pooling)
     gen = torch.Generator().manual_seed(5 + mode)
     for H in (64, 384, 768, 1024):
@@ -87,7 +86,7 @@ def test_pool_kernels_match_torch(pooling, normalize):
             ref = st_pool(t, mask, pooling, normalize)
             demb = torch.randn(ref.shape, generator=gen).cuda()
             ref.backward(demb)
-            emb, pooled, argmax = pool_fwd(tok, mask, mode, normalize, H)
+            emb, pooled, argmax = pool_fwd(lib, tok, mask, mode, normalize, H)
             torch.testing.assert_close(emb, ref.detach(), rtol=1e-5, atol=1e-6, msg=f"fwd H={H} L={L}")
             torch.testing.assert_close(pooled, st_pool(tok, mask, pooling, False), rtol=1e-5, atol=1e-6)
             if mode & 2:
@@ -95,11 +94,11 @@ def test_pool_kernels_match_torch(pooling, normalize):
                 ref_idx = tok.masked_fill(~m, -1e9).max(1).indices.to(torch.int32)
                 ref_idx[mask.sum(1) == 0] = -1
                 assert torch.equal(argmax, ref_idx)
-            dtok = pool_bwd(demb, pooled, argmax, mask, mode, normalize, L, H)
+            dtok = pool_bwd(lib, demb, pooled, argmax, mask, mode, normalize, L, H)
             torch.testing.assert_close(dtok, t.grad, rtol=1e-5, atol=1e-6, msg=f"bwd H={H} L={L}")
 
 
-def test_max_ties_go_to_the_lowest_token_index():
+def test_max_ties_go_to_the_lowest_token_index(lib):
     """Tied maxima, in rows owned by one wave (1, 9) and by different waves (2, 5, 13 / 7, 3): the argmax is the lowest
     valid row and the column's whole gradient lands there."""
     n, L, H = 2, 32, 64
@@ -112,38 +111,37 @@ def test_max_ties_go_to_the_lowest_token_index():
         tok[:, r, 1] = 3.0
     for r in (7, 3):
         tok[:, r, 2] = 1.5
-    emb, pooled, argmax = pool_fwd(tok, mask, 2, False, H)
+    emb, pooled, argmax = pool_fwd(lib, tok, mask, 2, False, H)
     assert argmax[:, :3].tolist() == [[2, 1, 3], [2, 1, 7]]
     demb = torch.randn(n, H).cuda()
-    dtok = pool_bwd(demb, pooled, argmax, mask, 2, False, L, H)
+    dtok = pool_bwd(lib, demb, pooled, argmax, mask, 2, False, L, H)
     for s in range(n):
         for c, r in zip(range(3), argmax[s, :3].tolist()):
             col = dtok[s, :, c]
             assert col[r] == demb[s, c] and int((col != 0).sum()) == 1
 
 
-def test_mean_head_on_the_new_kernels_agrees_with_the_old_pair():
+def test_mean_head_on_the_new_kernels_agrees_with_the_old_pair(lib):
     gen = torch.Generator().manual_seed(2)
     for H, L in ((384, 128), (1024, 512)):
         for normalize in (False, True):
             n = 8
             tok = torch.randn(n, L, H, generator=gen).cuda()
             mask = ragged_mask(n, L, gen).cuda()
-            lib = _lib.load()
             e_old, p_old = torch.empty(n, H, device="cuda"), torch.empty(n, H, device="cuda")
             _lib.check(lib.qst_pool_norm_fwd(tok.data_ptr(), mask.data_ptr(), n, L, H, int(normalize), e_old.data_ptr(),
                                              p_old.data_ptr(), _lib.current_stream_ptr()))
-            emb, pooled, argmax = pool_fwd(tok, mask, 4, normalize, H)
+            emb, pooled, argmax = pool_fwd(lib, tok, mask, 4, normalize, H)
             torch.testing.assert_close(emb, e_old, rtol=1e-5, atol=1e-6)
             demb = torch.randn(n, H, generator=gen).cuda()
             d_old = torch.empty(n, L, H, device="cuda")
             _lib.check(lib.qst_pool_norm_bwd(demb.data_ptr(), p_old.data_ptr(), mask.data_ptr(), n, L, H, int(normalize),
                                              d_old.data_ptr(), _lib.current_stream_ptr()))
-            torch.testing.assert_close(pool_bwd(demb, pooled, argmax, mask, 4, normalize, L, H), d_old, rtol=1e-5, atol=1e-6)
+            torch.testing.assert_close(pool_bwd(lib, demb, pooled, argmax, mask, 4, normalize, L, H), d_old, rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.parametrize("precision", ["bf16", "bf16x3"])
-def test_default_encoder_still_runs_the_old_mean_kernel(precision):
+def test_default_encoder_still_runs_the_old_mean_kernel(lib, precision):
     """An encoder left at the default head: its embeddings are BITWISE those of qst_pool_norm_fwd on its own token states."""
     cfg = PRESETS["tiny-bert"]
     enc = HipEncoder(cfg, device="cuda:0")
@@ -152,7 +150,6 @@ def test_default_encoder_still_runs_the_old_mean_kernel(precision):
     emb, tok, _ = enc.forward(ids, mask, types, want_tokens=True, precision=precision)
     n, L, H = tok.shape
     ref = torch.empty(n, H, device="cuda")
-    lib = _lib.load()
     _lib.check(lib.qst_pool_norm_fwd(tok.data_ptr(), mask.data_ptr(), n, L, H, 1, ref.data_ptr(), None, _lib.current_stream_ptr()))
     assert torch.equal(emb, ref)
     assert lib.qst_encoder_embedding_dim(enc.handle) == H
@@ -176,10 +173,8 @@ def test_encoder_heads_match_st_on_the_hf_token_states(golden_dir, pooling):
         enc.load_arena(synthetic_params(cfg, seed=14, **wkw))
         ids, mask, types = golden_inputs(key, cfg, B, L)
         n = 4 * B
-        ids_t, mask_t = torch.from_numpy(ids).view(n, L), torch.from_numpy(mask).view(n, L)
-        types_t = torch.from_numpy(types).view(n, L) if cfg.type_vocab_size > 0 else None
-        emb, tok, _ = enc.forward(ids_t.cuda(), mask_t.cuda(), None if types_t is None else types_t.cuda(), want_tokens=True,
-                                  precision="bf16x3")
+        mask_t = torch.from_numpy(mask).view(n, L)
+        emb, tok, _ = enc.forward(*quad_batch(cfg, ids, mask, types, B, L), want_tokens=True, precision="bf16x3")
         assert emb.shape == (n, cfg.embedding_dim)
         hf_tok = torch.from_numpy(g[key + "_tok"]).view(n, L, cfg.hidden_size)
         ref = st_pool(hf_tok, mask_t, pooling, cfg.normalize)

@@ -13,35 +13,12 @@ import quadruplet_sentence_transformer_amd  # noqa: E402,F401
 from quadruplet_sentence_transformer_amd import _lib  # noqa: E402
 from oracle import dropout_ref as D  # noqa: E402
 from oracle import torch_ref as R  # noqa: E402
+from kernel_helpers import OPDT, drop_desc, drop_state, kf, lib, op, ptr, stage_major, stream  # noqa: E402,F401
 
 BAD_ARG, UNSUPPORTED = -1, -2
 ARCH_BERT, ARCH_MPNET, ARCH_ROBERTA = 0, 1, 2
-OPDT = {"bf16": torch.bfloat16, "f16": torch.float16}
 MANT = {"bf16": 7, "f16": 10}                  # explicit significand bits of the operand type
 F16_MAX = 65504.0
-
-
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-@pytest.fixture(params=["bf16", "f16"])
-def op(request):
-    return request.param
-
-
-def kf(lib, name, op):
-    return _lib.kfn(lib, name, op)
-
-
-def stream():
-    return _lib.current_stream_ptr()
-
-
-def p(t):
-    return None if t is None else t.data_ptr()
 
 
 def bits(t):
@@ -64,20 +41,6 @@ def op_ulp(op, x):
     e = torch.frexp(x.clamp_min(1e-300)).exponent - 1              # floor(log2 |x|)
     emin = -14 if op == "f16" else -126
     return torch.ldexp(torch.ones_like(x), e.clamp_min(emin) - MANT[op])
-
-
-def drop_state(lib, seed, step):
-    st = torch.zeros(4, dtype=torch.int32, device="cuda")
-    _lib.check(lib.qst_dropout_init(st.data_ptr(), seed, stream()))
-    for _ in range(step):
-        _lib.check(lib.qst_dropout_advance(st.data_ptr(), stream()))
-    return st
-
-
-def drop_desc(st, site, prob):
-    d = _lib.QstDrop()
-    d.state, d.site, d.thr16 = st.data_ptr(), site, D.thr16_of(prob)
-    return d
 
 
 # ------------------------------------------------------------------ position ids
@@ -202,7 +165,7 @@ class Emb:
 
     def args(self):
         d = self.d
-        return (p(d["ids"]), p(d["tid"]), p(d["pos"]), p(d["word"]), p(d["pe"]), p(d["te"]), p(d["gamma"]), p(d["beta"]))
+        return (ptr(d["ids"]), ptr(d["tid"]), ptr(d["pos"]), ptr(d["word"]), ptr(d["pe"]), ptr(d["te"]), ptr(d["gamma"]), ptr(d["beta"]))
 
 
 def outs(M, H, op="bf16"):
@@ -296,14 +259,6 @@ def test_embed_ln_fwd_drop_matches_the_oracle_masks(lib, op, M, H):
     torch.testing.assert_close(y1c.double(), yr * mk.double(), rtol=1e-5, atol=1e-5 * float(mk.max()))
 
 
-def stage_major(s_rowmajor):
-    """[rows, K/32] scale bytes -> the library's layout [ceil(K/128)][rows][4] (zero-padded), flattened"""
-    rows, nb = s_rowmajor.shape
-    pad = (-nb) % 4
-    t = torch.nn.functional.pad(s_rowmajor, (0, pad))
-    return t.view(rows, (nb + pad) // 4, 4).permute(1, 0, 2).contiguous().view(-1)
-
-
 def mx_outs(M, H):
     return (torch.empty(M, H, dtype=torch.uint8, device="cuda"),
             torch.zeros((H + 127) // 128 * M * 4, dtype=torch.uint8, device="cuda"))
@@ -365,7 +320,7 @@ def test_embed_ln_refuses_shapes_it_is_not_built_for(lib, op):
                                                rs.data_ptr(), stream()) == want, H
         assert kf(lib, "qst_embed_ln_fwd_drop", op)(*e.args(), 1e-12, M, H, y.data_ptr(), yb.data_ptr(), xh.data_ptr(),
                                                     rs.data_ptr(), None, stream()) == want, H
-        assert kf(lib, "qst_ln_fwd", op)(p(e.d["word"]), p(e.d["gamma"]), p(e.d["beta"]), 1e-12, M, H, y.data_ptr(),
+        assert kf(lib, "qst_ln_fwd", op)(ptr(e.d["word"]), ptr(e.d["gamma"]), ptr(e.d["beta"]), 1e-12, M, H, y.data_ptr(),
                                          yb.data_ptr(), xh.data_ptr(), rs.data_ptr(), stream()) == want, H
     if op == "bf16":
         for H in (100, 96, 672):
@@ -376,7 +331,7 @@ def test_embed_ln_refuses_shapes_it_is_not_built_for(lib, op):
             yq, ys = mx_outs(M, H)
             assert lib.qst_embed_ln_fwd_mx_train(*e.args(), 1e-12, M, H, y.data_ptr(), yb.data_ptr(), xh.data_ptr(),
                                                  rs.data_ptr(), yq.data_ptr(), ys.data_ptr(), None, stream()) == UNSUPPORTED
-            assert lib.qst_ln_fwd_mx_train(p(e.d["word"]), p(e.d["gamma"]), p(e.d["beta"]), 1e-12, M, H, y.data_ptr(),
+            assert lib.qst_ln_fwd_mx_train(ptr(e.d["word"]), ptr(e.d["gamma"]), ptr(e.d["beta"]), 1e-12, M, H, y.data_ptr(),
                                            yb.data_ptr(), xh.data_ptr(), rs.data_ptr(), yq.data_ptr(), ys.data_ptr(),
                                            stream()) == UNSUPPORTED
 
