@@ -1,3 +1,4 @@
-from quadruplet_sentence_transformer_amd.evaluation import (InformationRetrievalEvaluator,  # noqa: F401
+from quadruplet_sentence_transformer_amd.evaluation import (EmbeddingSimilarityEvaluator,  # noqa: F401
+                                                            InformationRetrievalEvaluator,
                                                             SentenceEvaluator, SequentialEvaluator,
                                                             SimilarityFunction, TripletEvaluator)

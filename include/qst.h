@@ -229,6 +229,47 @@ int qst_quadruplet_loss(const float* xa, const float* xp, const float* xq, const
                         float* scratch, void* stream);
 
 /*
+ * The row-wise pair and triplet objectives of sentence-transformers 2.2.2 (version 103; csrc/tuple_loss.hip): what
+ * losses.CosineSimilarityLoss, ContrastiveLoss, OnlineContrastiveLoss and TripletLoss compute on the embeddings, and the
+ * per-row metric evaluation.EmbeddingSimilarityEvaluator scores with, each value and its autograd in one launch per stage.
+ * All tensors fp32, rows contiguous (stride D); any B >= 1, D >= 1. Metrics follow torch:
+ *   COS_SIM   u.v / (max(|u|_2, 1e-8) * max(|v|_2, 1e-8))     (F.cosine_similarity: each norm clamped on its own)
+ *   COS_DIST  1 - COS_SIM
+ *   L2, L1    |u - v + 1e-6|_p                                 (F.pairwise_distance: eps added to the difference)
+ *   DOT       u.v
+ *   L2_PLAIN, L1_PLAIN   |u - v|_p                             (sklearn's paired distances; gradient 0 where u == v)
+ * grad_* all NULL = forward only (nothing else is written); some but not all NULL is QST_ERR_BAD_ARG. reduction and
+ * grad_out as qst_quadruplet_loss: out [B] and grad_out [B] (NULL = ones) for QST_REDUCE_NONE, out [1] and grad_out [1]
+ * or NULL otherwise; sum / mean go through a fixed-order second stage (no atomics: results are bit-reproducible).
+ */
+enum { QST_METRIC_COS_SIM = 0, QST_METRIC_COS_DIST = 1, QST_METRIC_L2 = 2, QST_METRIC_L1 = 3, QST_METRIC_DOT = 4,
+       QST_METRIC_L2_PLAIN = 5, QST_METRIC_L1_PLAIN = 6 };
+enum { QST_PAIR_MSE = 0, QST_PAIR_CONTRASTIVE = 1, QST_PAIR_ONLINE_CONTRASTIVE = 2 };
+/* out[b] = metric(u[b], v[b]); with grad_u / grad_v: grad_out[b] * d(out[b]) / d(u[b]), d(v[b]). Any metric. */
+int qst_pair_metric(const float* u, const float* v, int B, int D, int metric, float* out,
+                    const float* grad_out, float* grad_u, float* grad_v, void* stream);
+/* labels fp32 [B]; m = metric(u, v) per row:
+ *   QST_PAIR_MSE                 (m - label)^2, metric = QST_METRIC_COS_SIM            (CosineSimilarityLoss, MSELoss)
+ *   QST_PAIR_CONTRASTIVE         0.5 * (label * m^2 + (1 - label) * relu(margin - m)^2)
+ *   QST_PAIR_ONLINE_CONTRASTIVE  with poss = m[label == 1], negs = m[label == 0],
+ *                                t_neg = max(poss) if |poss| > 1 else mean(negs), t_pos = min(negs) if |negs| > 1 else mean(poss):
+ *                                sum(poss[poss > t_pos]^2) + sum(relu(margin - negs[negs < t_neg])^2). ALWAYS a sum: out [1],
+ *                                grad_out [1] or NULL, `reduction` is not looked at beyond its range. The thresholds carry
+ *                                no gradient; rows with any other label take no part; the mean of an empty set is NaN
+ *                                and selects nothing.
+ * The two contrastive kinds take metric QST_METRIC_COS_DIST, QST_METRIC_L2 or QST_METRIC_L1; margin >= 0.
+ * scratch: fp32 [B + 2] (row values; for the online kind the distances and the two thresholds). May be NULL for
+ * QST_REDUCE_NONE of the first two kinds. */
+int qst_pair_loss(const float* u, const float* v, const float* labels, int B, int D, int kind, int metric,
+                  float margin, int reduction, float* out_loss, const float* grad_out,
+                  float* grad_u, float* grad_v, float* scratch, void* stream);
+/* relu(metric(a, p) - metric(a, n) + margin), metric QST_METRIC_COS_DIST, QST_METRIC_L2 or QST_METRIC_L1; margin >= 0.
+ * scratch: fp32 [B] (may be NULL for QST_REDUCE_NONE). */
+int qst_triplet_loss(const float* xa, const float* xp, const float* xn, int B, int D, int metric, float margin,
+                     int reduction, float* out_loss, const float* grad_out,
+                     float* grad_a, float* grad_p, float* grad_n, float* scratch, void* stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_grad_norm) + torch.optim.AdamW.step()
  * with ST fit()'s two parameter groups (/root/reference/training/main.py:128-148).
  *   n            : arena elements; decay is applied per segment as the layout says

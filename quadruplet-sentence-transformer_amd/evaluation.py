@@ -1,7 +1,7 @@
 """sentence_transformers.evaluation surface used by the reference's evaluators (models/evaluators.py:9-12,187-216,
 572-612; ir_evauation_script.py:107-131): the base class, SimilarityFunction, SequentialEvaluator, an encode()-driven
 TripletEvaluator and InformationRetrievalEvaluator, whose scoring + top-k run on the GPU
-through libqst (util.topk_scores)."""
+through libqst (util.topk_scores), and EmbeddingSimilarityEvaluator (graded pairs; qst_pair_metric)."""
 from __future__ import annotations
 
 import csv
@@ -74,6 +74,91 @@ class TripletEvaluator(SentenceEvaluator):
         if self.main_distance_function == SimilarityFunction.EUCLIDEAN:
             return acc_euc
         return max(acc_cos, acc_man, acc_euc)
+
+
+def average_ranks(x) -> np.ndarray:
+    """1-based ranks of x in ascending order, ties sharing the mean of the ranks they span (scipy.stats.rankdata)."""
+    x = np.asarray(x, dtype=np.float64).ravel()
+    order = np.argsort(x, kind="mergesort")
+    xs = x[order]
+    starts = np.r_[True, xs[1:] != xs[:-1]]
+    first = np.flatnonzero(starts)                              # first sorted position of every run of equal values
+    last = np.r_[first[1:], len(xs)] - 1
+    run = np.cumsum(starts) - 1
+    ranks = np.empty(len(x), dtype=np.float64)
+    ranks[order] = 0.5 * (first[run] + last[run]) + 1.0
+    return ranks
+
+
+def pearson(x, y) -> float:
+    x, y = np.asarray(x, dtype=np.float64).ravel(), np.asarray(y, dtype=np.float64).ravel()
+    xc, yc = x - x.mean(), y - y.mean()
+    den = np.sqrt((xc * xc).sum() * (yc * yc).sum())
+    return float((xc * yc).sum() / den) if den > 0 else float("nan")
+
+
+def spearman(x, y) -> float:
+    """Spearman's rank correlation: Pearson's r of the average ranks."""
+    return pearson(average_ranks(x), average_ranks(y))
+
+
+class EmbeddingSimilarityEvaluator(SentenceEvaluator):
+    """The STS evaluator of sentence-transformers 2.2.2: encode both sentence lists, score every pair by cosine
+    similarity, dot product and the negated Manhattan and Euclidean distances -- one qst_pair_metric launch per metric on
+    the device (st_losses.pair_metric; the distances are sklearn's paired distances, without torch's eps) -- and report
+    Pearson's and Spearman's correlation with the gold scores (host numpy; average ranks for ties). The return value is
+    the Spearman correlation of `main_similarity`, or the largest of the four when it is None."""
+
+    def __init__(self, sentences1: List[str], sentences2: List[str], scores: List[float], batch_size: int = 16,
+                 main_similarity: Optional[SimilarityFunction] = None, name: str = "", show_progress_bar: bool = False,
+                 write_csv: bool = True):
+        assert len(sentences1) == len(sentences2) == len(scores)
+        self.sentences1, self.sentences2, self.scores = sentences1, sentences2, scores
+        self.batch_size, self.main_similarity, self.name = batch_size, main_similarity, name
+        self.show_progress_bar, self.write_csv = show_progress_bar, write_csv
+        self.csv_file = "similarity_evaluation" + ("_" + name if name else "") + "_results.csv"
+        self.csv_headers = ["epoch", "steps", "cosine_pearson", "cosine_spearman", "euclidean_pearson", "euclidean_spearman",
+                            "manhattan_pearson", "manhattan_spearman", "dot_pearson", "dot_spearman"]
+
+    @classmethod
+    def from_input_examples(cls, examples, **kwargs):
+        return cls([ex.texts[0] for ex in examples], [ex.texts[1] for ex in examples], [ex.label for ex in examples],
+                   **kwargs)
+
+    def pair_scores(self, model) -> Dict[str, np.ndarray]:
+        """{'cosine', 'euclidean', 'manhattan', 'dot'} -> the similarity of every pair (distances negated), fp32 from
+        the device."""
+        import torch
+        from . import st_losses as S
+        e1 = model.encode(self.sentences1, batch_size=self.batch_size, show_progress_bar=self.show_progress_bar,
+                          convert_to_tensor=True)
+        e2 = model.encode(self.sentences2, batch_size=self.batch_size, show_progress_bar=self.show_progress_bar,
+                          convert_to_tensor=True)
+        out = {}
+        with torch.no_grad():
+            for key, metric, sign in (("cosine", S.METRIC_COS_SIM, 1.0), ("euclidean", S.METRIC_L2_PLAIN, -1.0),
+                                      ("manhattan", S.METRIC_L1_PLAIN, -1.0), ("dot", S.METRIC_DOT, 1.0)):
+                out[key] = sign * S.pair_metric(e1, e2, metric).cpu().numpy()
+        return out
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1) -> float:
+        sims = self.pair_scores(model)
+        res = {k: (pearson(self.scores, v), spearman(self.scores, v)) for k, v in sims.items()}
+        if output_path is not None and self.write_csv:
+            path = os.path.join(output_path, self.csv_file)
+            new = not os.path.isfile(path)
+            with open(path, "a", newline="", encoding="utf-8") as f:
+                w = csv.writer(f)
+                if new:
+                    w.writerow(self.csv_headers)
+                w.writerow([epoch, steps, *res["cosine"], *res["euclidean"], *res["manhattan"], *res["dot"]])
+        by_fn = {SimilarityFunction.COSINE: "cosine", SimilarityFunction.EUCLIDEAN: "euclidean",
+                 SimilarityFunction.MANHATTAN: "manhattan", SimilarityFunction.DOT_PRODUCT: "dot"}
+        if self.main_similarity is None:
+            return max(r[1] for r in res.values())
+        if self.main_similarity not in by_fn:
+            raise ValueError("Unknown main_similarity value")
+        return res[by_fn[self.main_similarity]][1]
 
 
 def ir_metrics(queries_result_list: List[List[dict]], queries_ids: List[str], relevant_docs: Dict[str, Set[str]],

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Union
 
 import torch
 
-from .sentence_transformer import InputExample, SentenceTransformer
+from .sentence_transformer import InputExample, SentenceTransformer, encode_columns_fused
 
 # dataset/constants.py keys of a quadruplet instance
 REFERENCE_EXAMPLE = "reference"
@@ -44,17 +44,7 @@ class QuadrupletSentenceTransformerLossModel(torch.nn.Module):
 
     def _encode_fused(self, cols):
         """Pad the four separately-padded columns to one length and run a single encoder pass."""
-        L = max(c["input_ids"].shape[1] for c in cols)
-        pad_id = self._st_model.cfg.pad_token_id
-
-        def cat(key, fill):
-            return torch.cat([torch.nn.functional.pad(c[key], (0, L - c[key].shape[1]), value=fill) for c in cols], 0)
-
-        feats = {"input_ids": cat("input_ids", pad_id), "attention_mask": cat("attention_mask", 0)}
-        if all("token_type_ids" in c for c in cols):
-            feats["token_type_ids"] = cat("token_type_ids", 0)
-        emb = self._st_model(feats)["sentence_embedding"]
-        return list(emb.split([c["input_ids"].shape[0] for c in cols], 0))
+        return encode_columns_fused(self._st_model, cols)
 
 
 def to_input_example(instance) -> InputExample:

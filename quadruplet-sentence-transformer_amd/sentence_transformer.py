@@ -708,6 +708,23 @@ def _shard_batch(features, labels, rank: int, world: int):
     return feats, labels[sel], n_total, int(sel.numel())
 
 
+def encode_columns_fused(st_model, cols) -> List[torch.Tensor]:
+    """The sentence embeddings of k separately-padded text columns from ONE [k*B, L] encoder pass: every column is padded
+    to the longest one's length (ids with the pad token, masks and type ids with 0), the pass runs once, and the result is
+    split back per column. Mathematically the k separate passes, a k-th of the launches."""
+    L = max(c["input_ids"].shape[1] for c in cols)
+    pad_id = st_model.cfg.pad_token_id
+
+    def cat(key, fill):
+        return torch.cat([torch.nn.functional.pad(c[key], (0, L - c[key].shape[1]), value=fill) for c in cols], 0)
+
+    feats = {"input_ids": cat("input_ids", pad_id), "attention_mask": cat("attention_mask", 0)}
+    if all("token_type_ids" in c for c in cols):
+        feats["token_type_ids"] = cat("token_type_ids", 0)
+    emb = st_model(feats)["sentence_embedding"]
+    return list(emb.split([c["input_ids"].shape[0] for c in cols], 0))
+
+
 def _loss_reduction(loss_model) -> str:
     for obj in (loss_model, getattr(loss_model, "_quadruplet_loss", None)):
         red = getattr(obj, "reduction", None)
