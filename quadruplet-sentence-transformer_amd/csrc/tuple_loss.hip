@@ -8,6 +8,12 @@
 //
 //   COS_SIM  u.v / (max(|u|, 1e-8) max(|v|, 1e-8))     COS_DIST 1 - COS_SIM     DOT u.v
 //   L2 / L1  |u - v + 1e-6|_p (torch pairwise_distance) L2_PLAIN / L1_PLAIN |u - v|_p
+//
+// The L1 sum runs in fp64. That distance grows with D (73.8 at D = 64), and the contrastive gradient of a negative is
+// (margin - d): a row 0.05 inside the margin turns the 0.8 ulp an fp32 sum of 64 terms is off by (6e-6) into 1.2e-4 of its
+// gradient, and among a few thousand rows some always lie that close. The L1 hinges take d as a double; what is stored and
+// returned stays fp32. L2 (sqrt(2 D) for random rows, 0.3 of the gradient tolerance on the same rows) and the cosine metrics
+// (bounded by 2) stay in fp32, bit for bit as before. The kernels stay HBM-bound.
 #include "qst_common.h"
 
 namespace {
@@ -29,24 +35,47 @@ struct TupleArgs {
     float margin, eps;
 };
 
-// metric class: 0 = products (cosine, dot), 1 = L2 of the difference, 2 = L1 of the difference
+// wave_sum (qst_common.h) on a double: the same tree, each half of the value moved by its own DPP / readlane
+template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double v) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xf, 0xf, true);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double lane_bcast_f64(double v, int lane) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    v += dpp_mov_f64<0xB1>(v);
+    v += dpp_mov_f64<0x4E>(v);
+    v += dpp_mov_f64<0x141>(v);
+    v += dpp_mov_f64<0x140>(v);
+    return (lane_bcast_f64(v, 0) + lane_bcast_f64(v, 16)) + (lane_bcast_f64(v, 32) + lane_bcast_f64(v, 48));
+}
+
+// metric class: 0 = products (cosine, dot), 1 = L2 of the difference, 2 = L1 of the difference (summed in fp64 into sd)
 template <int MC>
-__device__ __forceinline__ void accum(float x, float y, float eps, float (&s)[3]) {
+__device__ __forceinline__ void accum(float x, float y, float eps, float (&s)[3], double& sd) {
     if (MC == 0) { s[0] += x * y; s[1] += x * x; s[2] += y * y; }
-    else { const float t = x - y + eps; s[0] += (MC == 1) ? t * t : fabsf(t); }
+    else if (MC == 1) { const float t = x - y + eps; s[0] += t * t; }
+    else sd += fabs((double)x - (double)y + (double)eps);
 }
 
 // value m of a pair and the scalars of its gradient: MC 0: dm/dx = kxy*y + kxx*x, dm/dy = kxy*x + kyy*y;
 // MC 1: dm/dx = kxy * (x - y + eps) = -dm/dy (0 where the distance is 0, as torch's norm backward masks);
 // MC 2: dm/dx = sign(x - y + eps) = -dm/dy
-struct PairVal { float m, kxy, kxx, kyy; };
+// md: m before its rounding to fp32 (MC 2), for the hinges
+struct PairVal { float m, kxy, kxx, kyy; double md; };
 
 template <int MC>
-__device__ __forceinline__ PairVal finish(const float (&s)[3], int metric) {
-    PairVal r = {0.f, 0.f, 0.f, 0.f};
+__device__ __forceinline__ PairVal finish(const float (&s)[3], double sd, int metric) {
+    PairVal r = {0.f, 0.f, 0.f, 0.f, 0.0};
     if (MC == 0) {
         const float dot = wave_sum(s[0]);
-        if (metric == QST_METRIC_DOT) { r.m = dot; r.kxy = 1.f; return r; }
+        if (metric == QST_METRIC_DOT) { r.m = dot; r.kxy = 1.f; r.md = (double)dot; return r; }
         const float nx = sqrtf(wave_sum(s[1])), ny = sqrtf(wave_sum(s[2]));
         const float cx = fmaxf(nx, kCosEps), cy = fmaxf(ny, kCosEps);
         const float inv = 1.f / (cx * cy);
@@ -56,11 +85,14 @@ __device__ __forceinline__ PairVal finish(const float (&s)[3], int metric) {
         r.kxy = sg * inv;
         r.kxx = nx > kCosEps ? -sg * cs / (cx * cx) : 0.f;      // a clamped norm is a constant
         r.kyy = ny > kCosEps ? -sg * cs / (cy * cy) : 0.f;
+        r.md = (double)r.m;
     } else if (MC == 1) {
         r.m = sqrtf(wave_sum(s[0]));
+        r.md = (double)r.m;
         r.kxy = r.m > 0.f ? 1.f / r.m : 0.f;
     } else {
-        r.m = wave_sum(s[0]);
+        r.md = wave_sum_f64(sd);
+        r.m = (float)r.md;
         r.kxy = 1.f;
     }
     return r;
@@ -95,8 +127,9 @@ __global__ __launch_bounds__(256) void tuple_loss_kernel(TupleArgs a) {
 
     float xr[NX][VEC ? kVec * 4 : 1];
     float s[NP][3];
+    double sd[NP];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) { s[p][0] = 0.f; s[p][1] = 0.f; s[p][2] = 0.f; }
+    for (int p = 0; p < NP; ++p) { s[p][0] = 0.f; s[p][1] = 0.f; s[p][2] = 0.f; sd[p] = 0.0; }
 
     if (VEC) {
         const int nv = D >> 2;
@@ -116,7 +149,7 @@ __global__ __launch_bounds__(256) void tuple_loss_kernel(TupleArgs a) {
                 for (int k = 0; k < NX; ++k) xr[k][i * 4 + j] = X[k][j];
                 if (in) {
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) accum<MC>(X[0][j], X[p + 1][j], eps, s[p]);
+                    for (int p = 0; p < NP; ++p) accum<MC>(X[0][j], X[p + 1][j], eps, s[p], sd[p]);
                 }
             }
         }
@@ -124,18 +157,18 @@ __global__ __launch_bounds__(256) void tuple_loss_kernel(TupleArgs a) {
         for (int i = lane; i < D; i += 64) {
             const float x0 = a.x[0][base + i];
 #pragma unroll
-            for (int p = 0; p < NP; ++p) accum<MC>(x0, a.x[p + 1][base + i], eps, s[p]);
+            for (int p = 0; p < NP; ++p) accum<MC>(x0, a.x[p + 1][base + i], eps, s[p], sd[p]);
         }
     }
     PairVal pv[NP];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) pv[p] = finish<MC>(s[p], a.metric);
+    for (int p = 0; p < NP; ++p) pv[p] = finish<MC>(s[p], sd[p], a.metric);
 
     // row value and d(row value)/d(pair metric)
     float val, c[NP];
     const float m = pv[0].m;
     if (NX == 3) {
-        const float h = m - pv[1].m + a.margin;
+        const float h = MC == 2 ? (float)(pv[0].md - pv[NP - 1].md + (double)a.margin) : m - pv[NP - 1].m + a.margin;
         val = fmaxf(h, 0.f);
         c[0] = h > 0.f ? 1.f : 0.f;                 // F.relu passes no gradient at 0
         c[NP - 1] = -c[0];
@@ -144,7 +177,7 @@ __global__ __launch_bounds__(256) void tuple_loss_kernel(TupleArgs a) {
         switch (a.mode) {
             case MODE_MSE: val = (m - y) * (m - y); c[0] = 2.f * (m - y); break;
             case MODE_CONTRASTIVE: {
-                const float r = fmaxf(a.margin - m, 0.f);
+                const float r = MC == 2 ? (float)fmax((double)a.margin - pv[0].md, 0.0) : fmaxf(a.margin - m, 0.f);
                 val = 0.5f * (y * m * m + (1.f - y) * r * r);
                 c[0] = y * m - (1.f - y) * r;
                 break;
@@ -154,7 +187,8 @@ __global__ __launch_bounds__(256) void tuple_loss_kernel(TupleArgs a) {
                 const float dsel = a.sel[row], t_pos = a.sel[a.B], t_neg = a.sel[a.B + 1];
                 val = m; c[0] = 0.f;
                 if (y == 1.f && dsel > t_pos) c[0] = 2.f * m;
-                else if (y == 0.f && dsel < t_neg) c[0] = -2.f * fmaxf(a.margin - m, 0.f);
+                else if (y == 0.f && dsel < t_neg)
+                    c[0] = -2.f * (MC == 2 ? (float)fmax((double)a.margin - pv[0].md, 0.0) : fmaxf(a.margin - m, 0.f));
                 break;
             }
             default: val = m; c[0] = 1.f; break;    // MODE_METRIC, MODE_ONLINE_FWD
