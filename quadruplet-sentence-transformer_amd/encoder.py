@@ -7,6 +7,7 @@ streams only (ownership rule).
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -18,6 +19,67 @@ from .config import EncoderConfig, build_layout, hf_param_views, pooling_mask
 
 def _round_up(n: int, m: int) -> int:
     return (n + m - 1) // m * m
+
+
+@dataclass(frozen=True)
+class _Precision:
+    """What HipEncoder knows about one precision of include/qst.h. A further precision is one more row of _PRECISIONS."""
+    name: str
+    aliases: tuple
+    code: int                                  # QST_PREC_*
+    shadow_size: Optional[str] = None          # the size call of its operand shadow, on its own config (None: no shadow)
+    shadow_dtype: Optional[torch.dtype] = None
+    refresh: Optional[str] = None              # the entry point that fills the shadow from the fp32 parameters
+    bwd_shadow: str = "bf16"                   # the precision whose shadow its BACKWARD reads
+    train_needs_bf16: bool = False             # a training forward / a backward also wants the bf16 shadow fresh
+    train_saved: str = "saved"                 # the shared arena a training forward keeps its activations in
+    bwd_ws: str = "ws"                         # the shared arena of the backward's workspace
+
+
+_PRECISIONS = (
+    _Precision("bf16", (0, None), 0, "qst_shadow_elems", torch.bfloat16, refresh="qst_refresh_shadow"),
+    # the fp32-class parity path over the SAME arenas: no shadow of its own, activation arena / scratch apart from bf16's
+    _Precision("bf16x3", (1,), 1, train_saved="saved_x3", bwd_ws="ws_x3"),
+    # MXFP8 weights (e4m3 + one E8M0 scale per 32 input features) and activations on the fp8 matrix cores; its backward runs
+    # on the bf16 shadows
+    _Precision("fp8", (3,), 3, "qst_shadow8_bytes", torch.uint8, refresh="qst_refresh_shadow_mx", train_needs_bf16=True,
+               train_saved="saved_x3"),
+    # the bf16 kernels compiled on IEEE half: [W | W^T] of every Linear weight as f16
+    _Precision("f16", ("fp16", 4), 4, "qst_shadow_elems", torch.float16, refresh="qst_refresh_shadow", bwd_shadow="f16"),
+    # f16 with split weights (hi + lo) in the forward: shadow = [f16 arena | low halves]
+    _Precision("f16w", (5,), 5, "qst_shadow_elems", torch.float16, refresh="qst_refresh_shadow", bwd_shadow="f16w"),
+)
+_BY_ALIAS = {a: p for p in _PRECISIONS for a in (p.name, *p.aliases)}
+
+
+def _precision(precision) -> _Precision:
+    try:
+        return _BY_ALIAS[precision]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown precision {precision!r} (bf16 | f16 | f16w | bf16x3 | fp8)") from None
+
+
+@dataclass
+class _Live:
+    """One created precision of one encoder: its handle over the shared arenas, its operand shadow and whether the
+    parameters have changed since that shadow was filled."""
+    spec: _Precision
+    handle: object
+    shadow: Optional[torch.Tensor]
+    stale: bool = True
+
+
+def _stale_flag(name: str) -> property:
+    """shadow*_stale of precision `name`, readable and assignable whether or not that precision exists yet (it appears stale)."""
+    def get(self) -> bool:
+        rec = self._live.get(name)
+        return True if rec is None else rec.stale
+
+    def put(self, stale) -> None:
+        rec = self._live.get(name)
+        if rec is not None:
+            rec.stale = bool(stale)
+    return property(get, put)
 
 
 class HipEncoder:
@@ -34,57 +96,79 @@ class HipEncoder:
         if n != self.total:
             raise _lib.QstError(f"arena layout mismatch: python {self.total} vs libqst {n}")
         self.pool_mode = pooling_mask(cfg.pooling)     # include/qst.h QST_POOL_*: set on every handle this encoder creates
-        self.handle = self._create(self.ccfg, "qst_encoder_create")
-        self.emb_dim = self.lib.qst_encoder_embedding_dim(self.handle)
-        if self.emb_dim != cfg.embedding_dim:
-            raise _lib.QstError(f"embedding width mismatch: python {cfg.embedding_dim} vs libqst {self.emb_dim}")
         self.dropout = None           # (p_hidden, p_attn, seed) once set_dropout() switched it on
         self.dropout_step = 0
         self.drop_state = None
-        self.handle_x3 = None         # QST_PREC_BF16X3 handle over the SAME arenas, created on first use
-        self.handle_mx = None         # QST_PREC_FP8 handle (MXFP8 weights and activations on the fp8 matrix cores, inference)
-        self.handle_f16 = None        # QST_PREC_F16 handle: the bf16 kernels compiled on IEEE half (round 5), its own shadow
-        self.shadow_f16: Optional[torch.Tensor] = None
-        self.shadow_f16_stale = True
-        self.handle_f16w = None       # QST_PREC_F16W: f16 with split weights (hi + lo) in the forward; shadow = [f16 arena | low halves]
-        self.shadow_f16w: Optional[torch.Tensor] = None
-        self.shadow_f16w_stale = True
+        self.ln_fusion = 0
+        self._live: Dict[str, _Live] = {}       # canonical precision name -> what exists of it; created on first use
+        self._record("bf16")
+        self.emb_dim = self.lib.qst_encoder_embedding_dim(self.handle)
+        if self.emb_dim != cfg.embedding_dim:
+            raise _lib.QstError(f"embedding width mismatch: python {cfg.embedding_dim} vs libqst {self.emb_dim}")
         self.amp_scaler: Optional[torch.Tensor] = None   # device fp32 [4] {loss scale, growth tracker, last skipped, #skipped}
         self._step2_dev: Optional[torch.Tensor] = None   # device int64 [2] {optimiser steps, scheduler steps} of the amp step
-        self.shadow_mx: Optional[torch.Tensor] = None
-        self.shadow_mx_stale = True
         self.params = torch.zeros(self.total, dtype=torch.float32, device=self.device)
         self.grads: Optional[torch.Tensor] = None
         self.exp_avg: Optional[torch.Tensor] = None
         self.exp_avg_sq: Optional[torch.Tensor] = None
-        self.shadow = torch.zeros(self.lib.qst_shadow_elems(self.ccfg), dtype=torch.bfloat16, device=self.device)
-        self.shadow_stale = True
-        self._saved: Optional[torch.Tensor] = None
-        self._ws: Optional[torch.Tensor] = None
-        self._saved_x3: Optional[torch.Tensor] = None      # activation arena / scratch of the bf16x3 training path
-        self._ws_x3: Optional[torch.Tensor] = None
+        self._arenas: Dict[str, torch.Tensor] = {}        # shared byte arenas by name (_Precision.train_saved / .bwd_ws)
         self._scratch = torch.zeros(2048, dtype=torch.float32, device=self.device)
         self._step_dev: Optional[torch.Tensor] = None    # device-side optimiser step counter (graph-captured steps)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.opt_step = 0
 
     def _create(self, ccfg, what: str):
-        """A new encoder handle with this encoder's pooling head."""
+        """A new encoder handle with this encoder's pooling head, dropout setting (same rates, same device counter) and
+        ln_fusion: the one place where a handle created late inherits what the earlier ones were told."""
         h = _lib.vp()
         _lib.check(self.lib.qst_encoder_create(ccfg, h), what)
-        if self.pool_mode != pooling_mask("mean"):
-            st = self.lib.qst_encoder_set_pooling(h, self.pool_mode)
-            if st != 0:
-                self.lib.qst_encoder_destroy(h)
-                _lib.check(st, "qst_encoder_set_pooling")
+        try:
+            if self.pool_mode != pooling_mask("mean"):
+                _lib.check(self.lib.qst_encoder_set_pooling(h, self.pool_mode), "qst_encoder_set_pooling")
+            if self.dropout is not None:
+                _lib.check(self.lib.qst_encoder_set_dropout(h, self.dropout[0], self.dropout[1], self.drop_state.data_ptr()),
+                           "qst_encoder_set_dropout")
+            if self.ln_fusion:
+                _lib.check(self.lib.qst_encoder_set_ln_fusion(h, self.ln_fusion), "qst_encoder_set_ln_fusion")
+        except Exception:
+            self.lib.qst_encoder_destroy(h)
+            raise
         return h
+
+    def _record(self, precision) -> _Live:
+        """The live record of `precision` (a name or alias of _PRECISIONS), created on first use: an encoder that never runs
+        a precision allocates nothing for it."""
+        spec = _precision(precision)
+        rec = self._live.get(spec.name)
+        if rec is None:
+            ccfg = self.ccfg if spec.name == "bf16" else _lib.make_config(self.cfg, spec.code)
+            h = self._create(ccfg, f"qst_encoder_create({spec.name})")
+            try:
+                shadow = None if spec.shadow_size is None else torch.zeros(
+                    getattr(self.lib, spec.shadow_size)(ccfg), dtype=spec.shadow_dtype, device=self.device)
+            except Exception:
+                self.lib.qst_encoder_destroy(h)
+                raise
+            rec = self._live[spec.name] = _Live(spec, h, shadow)
+        return rec
+
+    def _handle_for(self, precision):
+        return self._record(precision).handle
+
+    @property
+    def handle(self):
+        """The bf16 handle: the one the optimiser steps and set_ffn_chain go through."""
+        return self._live["bf16"].handle
+
+    shadow_stale = _stale_flag("bf16")
+    shadow_mx_stale = _stale_flag("fp8")
+    shadow_f16_stale = _stale_flag("f16")
+    shadow_f16w_stale = _stale_flag("f16w")
 
     def __del__(self):
         try:
-            for attr in ("handle", "handle_x3", "handle_mx", "handle_f16", "handle_f16w"):
-                if getattr(self, attr, None):
-                    self.lib.qst_encoder_destroy(getattr(self, attr))
-                    setattr(self, attr, None)
+            while self._live:
+                self.lib.qst_encoder_destroy(self._live.popitem()[1].handle)
         except Exception:
             pass
 
@@ -94,10 +178,7 @@ class HipEncoder:
         if t.numel() != self.total:
             raise ValueError(f"arena has {t.numel()} elements, expected {self.total}")
         self.params.copy_(t.to(self.device))
-        self.shadow_stale = True
-        self.shadow_mx_stale = True
-        self.shadow_f16_stale = True
-        self.shadow_f16w_stale = True
+        self.mark_stale()
 
     def named_views(self) -> Dict[str, torch.Tensor]:
         """HF-named views into the parameter arena (no copies)."""
@@ -136,14 +217,13 @@ class HipEncoder:
             raise ValueError("dropout probabilities must be in [0, 1)")
         on = p_hidden > 0.0 or p_attn > 0.0
         if on:
-            if getattr(self, "drop_state", None) is None:
+            if self.drop_state is None:
                 self.drop_state = torch.zeros(4, dtype=torch.int32, device=self.device)
             _lib.check(self.lib.qst_dropout_init(self.drop_state.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                  _lib.current_stream_ptr()), "qst_dropout_init")
-        for h in (self.handle, self.handle_mx, self.handle_x3, self.handle_f16, self.handle_f16w):      # every precision's training forward drops at the same places
-            if h is not None:
-                _lib.check(self.lib.qst_encoder_set_dropout(h, float(p_hidden), float(p_attn),
-                                                            self.drop_state.data_ptr() if on else None), "qst_encoder_set_dropout")
+        for rec in self._live.values():                 # every precision's training forward drops at the same places
+            _lib.check(self.lib.qst_encoder_set_dropout(rec.handle, float(p_hidden), float(p_attn),
+                                                        self.drop_state.data_ptr() if on else None), "qst_encoder_set_dropout")
         self.dropout = (float(p_hidden), float(p_attn), int(seed)) if on else None
         self.dropout_step = 0
 
@@ -155,9 +235,8 @@ class HipEncoder:
     def set_ln_fusion(self, mode: int) -> None:
         """Where a projection + LayerNorm (and a dgrad + LayerNorm backward) run as one kernel (include/qst.h
         qst_encoder_set_ln_fusion): 0 by size (default), 1 wherever such a kernel exists, 2 never. Every precision's handle."""
-        for h in (self.handle, self.handle_mx, self.handle_x3, self.handle_f16, self.handle_f16w):
-            if h is not None:
-                _lib.check(self.lib.qst_encoder_set_ln_fusion(h, int(mode)), "qst_encoder_set_ln_fusion")
+        for rec in self._live.values():
+            _lib.check(self.lib.qst_encoder_set_ln_fusion(rec.handle, int(mode)), "qst_encoder_set_ln_fusion")
         self.ln_fusion = int(mode)
 
     def set_dropout_step(self, step: int) -> None:
@@ -166,28 +245,23 @@ class HipEncoder:
             self.drop_state[2] = int(step)
             self.dropout_step = int(step)
 
-    def refresh_shadow_mx(self) -> None:
-        """Quantise every Linear weight to MXFP8 (e4m3 + one E8M0 scale per 32 input features; QST_PREC_FP8)."""
-        _lib.check(self.lib.qst_refresh_shadow_mx(self.handle_mx, self.params.data_ptr(), self.shadow_mx.data_ptr(),
-                                                  _lib.current_stream_ptr()), "qst_refresh_shadow_mx")
-        self.shadow_mx_stale = False
+    # ------------------------------------------------------------------ operand shadows
+    def refresh_shadow(self, precision="bf16") -> None:
+        """Fill the operand shadow of `precision` from the fp32 parameters: [W | W^T] of every Linear weight in bf16 / IEEE
+        half (f16w: and, behind it, the low halves of the split weights), or the MXFP8 quantisation (fp8)."""
+        rec = self._record(precision)
+        if rec.shadow is None:
+            raise ValueError(f"precision {rec.spec.name!r} has no operand shadow")
+        _lib.check(getattr(self.lib, rec.spec.refresh)(rec.handle, self.params.data_ptr(), rec.shadow.data_ptr(),
+                                                       _lib.current_stream_ptr()), f"{rec.spec.refresh}({rec.spec.name})")
+        rec.stale = False
 
-    def refresh_shadow_f16(self) -> None:
-        """[W | W^T] of every Linear weight as IEEE half (QST_PREC_F16: qst_refresh_shadow on that handle)."""
-        _lib.check(self.lib.qst_refresh_shadow(self.handle_f16, self.params.data_ptr(), self.shadow_f16.data_ptr(),
-                                               _lib.current_stream_ptr()), "qst_refresh_shadow(f16)")
-        self.shadow_f16_stale = False
-
-    def refresh_shadow_f16w(self) -> None:
-        """QST_PREC_F16W: the f16 [W | W^T] arena and, behind it, the low halves of the split weights."""
-        _lib.check(self.lib.qst_refresh_shadow(self.handle_f16w, self.params.data_ptr(), self.shadow_f16w.data_ptr(),
-                                               _lib.current_stream_ptr()), "qst_refresh_shadow(f16w)")
-        self.shadow_f16w_stale = False
-
-    def refresh_shadow(self) -> None:
-        _lib.check(self.lib.qst_refresh_shadow(self.handle, self.params.data_ptr(), self.shadow.data_ptr(),
-                                               _lib.current_stream_ptr()), "qst_refresh_shadow")
-        self.shadow_stale = False
+    def mark_stale(self, keep=None) -> None:
+        """The parameters changed: the shadow of every created precision is stale, except that of `keep`, which was refreshed
+        after the change (a replayed graph ends with that refresh)."""
+        fresh = None if keep is None else _precision(keep).name
+        for name, rec in self._live.items():
+            rec.stale = name != fresh
 
     # ------------------------------------------------------------------ shapes
     @staticmethod
@@ -203,68 +277,20 @@ class HipEncoder:
                 type_ids = torch.nn.functional.pad(type_ids, (0, Lp - L), value=0)
         return ids.contiguous(), mask.contiguous(), None if type_ids is None else type_ids.contiguous(), L
 
-    def _arena(self, attr: str, nbytes: int) -> torch.Tensor:
-        buf = getattr(self, attr)
+    def _arena(self, name: str, nbytes: int) -> torch.Tensor:
+        buf = self._arenas.get(name)
         if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            setattr(self, attr, buf)
+            buf = self._arenas[name] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return buf
 
+    def saved_bytes(self, precision, n: int, L: int, training: bool) -> int:
+        """Bytes of the activation arena a forward of [n, L] at `precision` fills (0: unsupported shape)."""
+        return self.lib.qst_encoder_saved_bytes(self._record(precision).handle, n, L, int(training))
+
+    def bwd_workspace_bytes(self, precision, n: int, L: int) -> int:
+        return self.lib.qst_encoder_bwd_workspace_bytes(self._record(precision).handle, n, L)
+
     # ------------------------------------------------------------------ forward / backward
-    def _handle_for(self, precision: str):
-        h = self._handle_for_raw(precision)
-        if getattr(self, "ln_fusion", 0) and not getattr(h, "_ln_fusion_set", None) == self.ln_fusion:
-            _lib.check(self.lib.qst_encoder_set_ln_fusion(h, self.ln_fusion), "qst_encoder_set_ln_fusion")
-            try:
-                h._ln_fusion_set = self.ln_fusion
-            except AttributeError:
-                pass
-        return h
-
-    def _handle_for_raw(self, precision: str):
-        if precision in ("bf16", 0, None):
-            return self.handle
-        if precision in ("fp8", 3):
-            if self.handle_mx is None:
-                h = self._create(_lib.make_config(self.cfg, 3), "qst_encoder_create(fp8)")
-                self.handle_mx = h
-                self.shadow_mx = torch.zeros(self.lib.qst_shadow8_bytes(self.ccfg), dtype=torch.uint8, device=self.device)
-                self.shadow_mx_stale = True
-                if self.dropout is not None:         # (created after set_dropout: same settings, same device counter)
-                    _lib.check(self.lib.qst_encoder_set_dropout(h, self.dropout[0], self.dropout[1], self.drop_state.data_ptr()),
-                               "qst_encoder_set_dropout")
-            return self.handle_mx
-        if precision in ("f16", "fp16", 4):
-            if self.handle_f16 is None:
-                h = self._create(_lib.make_config(self.cfg, 4), "qst_encoder_create(f16)")
-                self.handle_f16 = h
-                self.shadow_f16 = torch.zeros(self.lib.qst_shadow_elems(self.ccfg), dtype=torch.float16, device=self.device)
-                self.shadow_f16_stale = True
-                if self.dropout is not None:
-                    _lib.check(self.lib.qst_encoder_set_dropout(h, self.dropout[0], self.dropout[1], self.drop_state.data_ptr()),
-                               "qst_encoder_set_dropout")
-            return self.handle_f16
-        if precision in ("f16w", 5):
-            if self.handle_f16w is None:
-                c5 = _lib.make_config(self.cfg, 5)
-                h = self._create(c5, "qst_encoder_create(f16w)")
-                self.handle_f16w = h
-                self.shadow_f16w = torch.zeros(self.lib.qst_shadow_elems(c5), dtype=torch.float16, device=self.device)
-                self.shadow_f16w_stale = True
-                if self.dropout is not None:
-                    _lib.check(self.lib.qst_encoder_set_dropout(h, self.dropout[0], self.dropout[1], self.drop_state.data_ptr()),
-                               "qst_encoder_set_dropout")
-            return self.handle_f16w
-        if precision not in ("bf16x3", 1):
-            raise ValueError(f"unknown precision {precision!r} (bf16 | f16 | f16w | bf16x3 | fp8)")
-        if self.handle_x3 is None:
-            h = self._create(_lib.make_config(self.cfg, 1), "qst_encoder_create(x3)")
-            self.handle_x3 = h
-            if self.dropout is not None:
-                _lib.check(self.lib.qst_encoder_set_dropout(h, self.dropout[0], self.dropout[1], self.drop_state.data_ptr()),
-                           "qst_encoder_set_dropout")
-        return self.handle_x3
-
     def forward(self, ids: torch.Tensor, mask: torch.Tensor, type_ids: Optional[torch.Tensor] = None,
                 training: bool = False, want_tokens: bool = False, saved: Optional[torch.Tensor] = None,
                 precision: str = "bf16"):
@@ -274,42 +300,38 @@ class HipEncoder:
         activations). training=True keeps what the matching backward(precision=...) needs."""
         assert ids.dtype == torch.int64 and mask.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
         n, L = ids.shape
-        handle = self._handle_for(precision)
-        if self.shadow_stale and (handle is self.handle or (training and handle is self.handle_mx)):
-            self.refresh_shadow()                    # (an fp8 training forward: its backward runs on the bf16 shadows)
-        shadow = self.shadow
-        if handle is self.handle_mx and handle is not None:
-            if self.shadow_mx_stale:
-                self.refresh_shadow_mx()
-            shadow = self.shadow_mx
-        if handle is self.handle_f16 and handle is not None:
-            if self.shadow_f16_stale:
-                self.refresh_shadow_f16()
-            shadow = self.shadow_f16
-        if handle is self.handle_f16w and handle is not None:
-            if self.shadow_f16w_stale:
-                self.refresh_shadow_f16w()
-            shadow = self.shadow_f16w
-        nbytes = self.lib.qst_encoder_saved_bytes(handle, n, L, int(training))
+        rec = self._record(precision)
+        if training and rec.spec.train_needs_bf16 and self.shadow_stale:
+            self.refresh_shadow("bf16")          # (an fp8 training forward: its backward runs on the bf16 shadows)
+        if rec.shadow is not None and rec.stale:
+            self.refresh_shadow(rec.spec.name)
+        # bf16x3 has no shadow and reads none: it is handed the bf16 buffer as it is
+        shadow = rec.shadow if rec.shadow is not None else self._live["bf16"].shadow
+        nbytes = self.saved_bytes(precision, n, L, training)
         if nbytes == 0:
             raise _lib.QstError(f"unsupported shape nseq={n} L={L} for this encoder (L % 32 == 0, L <= 512)")
         if saved is None:
-            saved = self._arena("_saved_x3" if handle in (self.handle_x3, self.handle_mx) and training else "_saved", nbytes)
+            saved = self._arena(rec.spec.train_saved if training else "saved", nbytes)
         emb = torch.empty(n, self.emb_dim, dtype=torch.float32, device=self.device)
         tok = torch.empty(n, L, self.cfg.hidden_size, dtype=torch.float32, device=self.device) if want_tokens else None
         _lib.check(self.lib.qst_encoder_forward(
-            handle, ids.data_ptr(), mask.data_ptr(), _lib.ptr(type_ids), n, L, self.params.data_ptr(),
+            rec.handle, ids.data_ptr(), mask.data_ptr(), _lib.ptr(type_ids), n, L, self.params.data_ptr(),
             shadow.data_ptr(), emb.data_ptr(), _lib.ptr(tok), saved.data_ptr(), saved.numel(), int(training),
             _lib.current_stream_ptr()), "qst_encoder_forward")
         if training and self.dropout is not None:
             self.dropout_step += 1           # mirrors the device counter (tests rebuild this step's masks from it)
         return emb, tok, saved
 
-    def shadow_for(self, handle) -> torch.Tensor:
-        """The [W | W^T] operand shadow a BACKWARD on `handle` reads: IEEE half for the f16 handle, bf16 otherwise."""
-        if handle is not None and handle is self.handle_f16w:
-            return self.shadow_f16w
-        return self.shadow_f16 if (handle is self.handle_f16 and handle is not None) else self.shadow
+    def backward_operands(self, precision, n: int, L: int, ws: Optional[torch.Tensor] = None):
+        """(handle, shadow, workspace) of a backward of [n, L] at `precision`: the [W | W^T] shadow the table names (IEEE half
+        for f16 / f16w, bf16 otherwise; refreshed if an fp8 backward finds it stale) and, unless the caller brings `ws`,
+        that precision's shared workspace."""
+        rec = self._record(precision)
+        if rec.spec.train_needs_bf16 and self.shadow_stale:
+            self.refresh_shadow("bf16")
+        if ws is None:
+            ws = self._arena(rec.spec.bwd_ws, self.bwd_workspace_bytes(precision, n, L))
+        return rec.handle, self._live[rec.spec.bwd_shadow].shadow, ws
 
     def backward(self, ids, mask, type_ids, grad_emb: torch.Tensor, saved: torch.Tensor, precision: str = "bf16") -> None:
         """Accumulate d(loss)/d(params) into self.grads given d(loss)/d(emb). precision="bf16x3": the fp32-class backward
@@ -317,32 +339,28 @@ class HipEncoder:
         backward over what a forward(training=True, precision="fp8") kept (fp8 forward GEMMs, bf16 dgrad / wgrad)."""
         self.ensure_train_state()
         n, L = ids.shape
-        handle = self._handle_for(precision)
-        if handle is self.handle_mx and self.shadow_stale:
-            self.refresh_shadow()                    # the backward's operands are the bf16 shadows
-        nws = self.lib.qst_encoder_bwd_workspace_bytes(handle, n, L)
-        ws = self._arena("_ws_x3" if handle is self.handle_x3 else "_ws", nws)
+        handle, shadow, ws = self.backward_operands(precision, n, L)
         grad_emb = grad_emb.contiguous()
         _lib.check(self.lib.qst_encoder_backward(
             handle, ids.data_ptr(), mask.data_ptr(), _lib.ptr(type_ids), n, L, self.params.data_ptr(),
-            self.shadow_for(handle).data_ptr(), grad_emb.data_ptr(), self.grads.data_ptr(), saved.data_ptr(), saved.numel(),
+            shadow.data_ptr(), grad_emb.data_ptr(), self.grads.data_ptr(), saved.data_ptr(), saved.numel(),
             ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), "qst_encoder_backward")
 
     def adamw_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
                    max_grad_norm: float = 1.0, grad_scale: float = 1.0) -> None:
         """clip_grad_norm_ + AdamW + zero_grad in one pass over the arena; the norm stays on the device."""
-        self.ensure_train_state()
         self.opt_step += 1
-        _lib.check(self.lib.qst_clip_adamw_step(
-            self.handle, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
-            self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, max_grad_norm, grad_scale,
-            self.opt_step, self.grad_norm.data_ptr(), self._scratch.data_ptr(), _lib.current_stream_ptr()),
-            "qst_clip_adamw_step")
-        self.shadow_stale = True
-        self.shadow_mx_stale = True
-        self.shadow_f16_stale = True
-        self.shadow_f16w_stale = True
+        self._clip_adamw("qst_clip_adamw_step", lr, betas, eps, weight_decay, max_grad_norm, grad_scale, self.opt_step)
 
+    def _clip_adamw(self, entry: str, lr, betas, eps, weight_decay, max_grad_norm, grad_scale, *extra) -> None:
+        """What the three optimiser steps share: the arenas and AdamW arguments in front of an entry point's own (`extra`),
+        the norm and scratch behind them, and every shadow stale afterwards."""
+        self.ensure_train_state()
+        _lib.check(getattr(self.lib, entry)(
+            self.handle, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
+            self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, max_grad_norm, grad_scale, *extra,
+            self.grad_norm.data_ptr(), self._scratch.data_ptr(), _lib.current_stream_ptr()), entry)
+        self.mark_stale()
 
     # ------------------------------------------------------------------ optimiser state (true resume, SURVEY.md 8f rank 3)
     def optimizer_state(self) -> Dict[str, torch.Tensor]:
@@ -367,20 +385,11 @@ class HipEncoder:
                          grad_scale: float = 1.0) -> None:
         """adamw_step with the WarmupLinear schedule and the step counter on the device (no per-step host value is a
         kernel argument, so the call can sit inside a captured HIP graph). The counter starts from self.opt_step."""
-        self.ensure_train_state()
         if self._step_dev is None:
             self._step_dev = torch.tensor([self.opt_step], dtype=torch.int64, device=self.device)
         self.opt_step += 1               # host mirror (bookkeeping only; the device counter is authoritative)
-        _lib.check(self.lib.qst_clip_adamw_step_sched(
-            self.handle, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
-            self.exp_avg_sq.data_ptr(), base_lr, betas[0], betas[1], eps, weight_decay, max_grad_norm, grad_scale,
-            int(warmup_steps), int(total_steps), self._step_dev.data_ptr(), self.grad_norm.data_ptr(),
-            self._scratch.data_ptr(), _lib.current_stream_ptr()), "qst_clip_adamw_step_sched")
-        self.shadow_stale = True
-        self.shadow_mx_stale = True
-        self.shadow_f16_stale = True
-        self.shadow_f16w_stale = True
-
+        self._clip_adamw("qst_clip_adamw_step_sched", base_lr, betas, eps, weight_decay, max_grad_norm, grad_scale,
+                         int(warmup_steps), int(total_steps), self._step_dev.data_ptr())
 
     # ------------------------------------------------------------------ mixed precision (QST_PREC_F16 training)
     def ensure_amp_scaler(self, init_scale: float = 65536.0) -> torch.Tensor:
@@ -399,21 +408,13 @@ class HipEncoder:
         (qst_clip_adamw_step_amp): the gradients in the arena carry the loss scale; a step whose gradients overflowed is
         skipped and halves the scale. total_steps <= 0: constant base_lr. No host value of the step depends on the outcome,
         so the call can sit inside a captured graph; self.opt_step counts CALLS (skipped steps are in amp_scaler[3])."""
-        self.ensure_train_state()
         self.ensure_amp_scaler()
         if self._step2_dev is None:
             self._step2_dev = torch.tensor([self.opt_step, self.opt_step], dtype=torch.int64, device=self.device)
         self.opt_step += 1
-        _lib.check(self.lib.qst_clip_adamw_step_amp(
-            self.handle, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-            base_lr, betas[0], betas[1], eps, weight_decay, max_grad_norm, grad_scale, int(warmup_steps), int(total_steps),
-            self._step2_dev.data_ptr(), self.amp_scaler.data_ptr(), growth_factor, backoff_factor, int(growth_interval),
-            self.grad_norm.data_ptr(), self._scratch.data_ptr(), _lib.current_stream_ptr()), "qst_clip_adamw_step_amp")
-        self.shadow_stale = True
-        self.shadow_mx_stale = True
-        self.shadow_f16_stale = True
-        self.shadow_f16w_stale = True
-
+        self._clip_adamw("qst_clip_adamw_step_amp", base_lr, betas, eps, weight_decay, max_grad_norm, grad_scale,
+                         int(warmup_steps), int(total_steps), self._step2_dev.data_ptr(), self.amp_scaler.data_ptr(),
+                         growth_factor, backoff_factor, int(growth_interval))
 
 def quadruplet_loss_raw(xa, xp, xq, xn, gamma, m_pn, m_pq, m_qn, p, swap, reduction: int,
                         grad_out: Optional[torch.Tensor] = None, want_grads: bool = False):

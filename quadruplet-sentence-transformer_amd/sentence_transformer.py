@@ -144,8 +144,7 @@ class _EncodeFn(torch.autograd.Function):
         prec = model.training_precision if training == 1 else "bf16"
         if training == 1:
             n, L = ids.shape
-            nbytes = enc.lib.qst_encoder_saved_bytes(enc._handle_for(prec), n, L, 1)
-            saved = torch.empty(nbytes, dtype=torch.uint8, device=enc.device)   # one arena per live graph
+            saved = torch.empty(enc.saved_bytes(prec, n, L, True), dtype=torch.uint8, device=enc.device)   # one arena per live graph
         # training == 2: a train()-mode pass without autograd (dropout on, nothing to keep): the shared activation arena
         emb, _, saved = enc.forward(ids, mask, types, training=bool(training), saved=saved, precision=prec)
         ctx.model, ctx.saved, ctx.inputs, ctx.prec = model, saved, (ids, mask, types), prec

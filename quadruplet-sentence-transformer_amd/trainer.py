@@ -91,17 +91,14 @@ def staged_backward(enc: HipEncoder, ids, mask, types, grad_emb, saved, ws=None,
     n, L = ids.shape
     if precision not in ("bf16", "fp8", "f16", "f16w", "bf16x3"):
         raise ValueError(f"unknown precision {precision!r}")
-    handle = enc._handle_for(precision)
-    x3 = precision == "bf16x3"
-    if ws is None:
-        ws = enc._arena("_ws_x3" if x3 else "_ws", lib.qst_encoder_bwd_workspace_bytes(handle, n, L))
+    handle, shadow, ws = enc.backward_operands(precision, n, L, ws)
     grad_emb = grad_emb.contiguous()
     N = enc.cfg.num_layers
 
     def stage(flags, hi, lo):
         _lib.check(lib.qst_encoder_backward_stage(
             handle, ids.data_ptr(), mask.data_ptr(), _lib.ptr(types), n, L, enc.params.data_ptr(),
-            enc.shadow_for(handle).data_ptr(), grad_emb.data_ptr(), enc.grads.data_ptr(), saved.data_ptr(), saved.numel(),
+            shadow.data_ptr(), grad_emb.data_ptr(), enc.grads.data_ptr(), saved.data_ptr(), saved.numel(),
             ws.data_ptr(), ws.numel(), int(flags), hi, lo, st), "qst_encoder_backward_stage")
 
     if buckets is None:
@@ -116,7 +113,7 @@ def staged_backward(enc: HipEncoder, ids, mask, types, grad_emb, saved, ws=None,
     for k, l in enumerate(range(N - 1, 0, -1)):                        # layers N-1 ... 1
         stage(BWD_HEAD if k == 0 else 0, l + 1, l)
         works += allreduce_ranges(enc.grads, [order[k]], group, async_op=True)
-    if x3:
+    if precision == "bf16x3":
         # the parity path has no postponed weight-gradient launch: layer 0 and the embeddings in one stage, then the same two
         # buckets in the same order (round 5: rounds 3-4 reduced everything after a one-call backward)
         stage((BWD_HEAD if N == 1 else 0) | BWD_EMBED, 1, 0)
@@ -237,8 +234,8 @@ class QuadrupletTrainer:
             n, L = 4 * ids4.shape[1], ids4.shape[2]
             enc = self.enc
             bufs = dict(
-                saved=torch.empty(enc.lib.qst_encoder_saved_bytes(enc._handle_for(self.precision), n, L, 1), dtype=torch.uint8, device=enc.device),
-                ws=torch.empty(enc.lib.qst_encoder_bwd_workspace_bytes(enc._handle_for(self.precision), n, L), dtype=torch.uint8, device=enc.device))
+                saved=torch.empty(enc.saved_bytes(self.precision, n, L, True), dtype=torch.uint8, device=enc.device),
+                ws=torch.empty(enc.bwd_workspace_bytes(self.precision, n, L), dtype=torch.uint8, device=enc.device))
             loss = self._step_eager(*static, sched_on_device=True, **bufs)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
@@ -253,10 +250,8 @@ class QuadrupletTrainer:
             static[2].copy_(types4, non_blocking=True)
         graph.replay()
         self.enc.opt_step += 1
-        # the captured step ends with the refresh of the operand shadow it trains on (the other one is stale)
-        self.enc.shadow_stale = self.precision != "bf16"
-        self.enc.shadow_f16_stale = self.precision != "f16"
-        self.enc.shadow_f16w_stale = self.precision != "f16w"
+        # the captured step ends with the refresh of the operand shadow it trains on (every other one is stale)
+        self.enc.mark_stale(keep=self.precision)
         self.sched_step += 1
         return static_loss
 
@@ -266,11 +261,8 @@ class QuadrupletTrainer:
         enc = self.enc
         loss, _, g, saved, (ids, mask, types) = self.forward_loss(ids4, mask4, types4, training=True, want_grads=True,
                                                                  saved=saved, precision=self.precision)
-        if self.precision == "bf16x3" and not (self.world > 1 or self.force_dp):
-            enc.backward(ids, mask, types, stacked(g), saved, precision="bf16x3")
-            works = []
-        elif self.precision == "fp8" and not (self.world > 1 or self.force_dp):
-            enc.backward(ids, mask, types, stacked(g), saved, precision="fp8")
+        if self.precision in ("bf16x3", "fp8") and not (self.world > 1 or self.force_dp):
+            enc.backward(ids, mask, types, stacked(g), saved, precision=self.precision)
             works = []
         else:
             works = staged_backward(enc, ids, mask, types, stacked(g), saved, ws,
@@ -278,25 +270,20 @@ class QuadrupletTrainer:
                                     precision=self.precision)
         for w in works:
             w.wait()
+        opt0 = enc.opt_step
         if self.amp:
-            opt0 = enc.opt_step
             enc.adamw_step_amp(self.lr, self.warmup_steps, self.total_steps, self.betas, self.eps, self.wd,
                                self.max_grad_norm, 1.0 / self.world, growth_interval=self.amp_growth_interval)
-            if sched_on_device:
-                # a graph replays the whole step: the next forward's operand refresh belongs inside it
-                enc.refresh_shadow_f16() if self.precision == "f16" else enc.refresh_shadow_f16w()
-            if not count:
-                enc.opt_step = opt0
         elif sched_on_device:
-            opt0 = enc.opt_step
             enc.adamw_step_sched(self.lr, self.warmup_steps, self.total_steps, self.betas, self.eps, self.wd,
                                  self.max_grad_norm, 1.0 / self.world)
-            # a graph replays the whole step, so the next forward's shadow refresh belongs inside it
-            enc.refresh_shadow()
-            if not count:
-                enc.opt_step = opt0          # capture pass: nothing executed
         else:
             enc.adamw_step(self.current_lr(), self.betas, self.eps, self.wd, self.max_grad_norm, 1.0 / self.world)
+        if sched_on_device:
+            # a graph replays the whole step, so the next forward's operand refresh belongs inside it
+            enc.refresh_shadow(self.precision)
+        if not count:
+            enc.opt_step = opt0              # capture pass: nothing executed
         if count:
             self.sched_step += 1
         return loss
