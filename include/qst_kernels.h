@@ -285,7 +285,15 @@ int qst_pool_bwd(const float* demb, const float* pooled, const int32_t* argmax, 
 int qst_attention_fwd(const void* qkv, const int64_t* mask, const float* rel_pos, int nseq, int L, int A, int d,
                       void* ctx, float* lse, void* stream);
 /* Backward: dctx bf16 [nseq*L, H] -> dqkv bf16 [nseq*L, 3H]; drel_pos f32 [A, 2L] += (or NULL; needs rel_pos).
- * delta_scratch: f32 [nseq, A, L] (dO.O per query, written by the dQ kernel, read by the dK/dV kernel). */
+ * delta_scratch: f32 [nseq, A, L] (dO.O per query, written by the dQ kernel, read by the dK/dV kernel).
+ * Masked keys: their dK and dV rows are exactly 0 in every sequence that has a valid key (HF's probabilities are exactly 0
+ * there, and so are the kernels'); padded QUERY rows attend like any other, as in HF, and get a dQ.
+ * A sequence with no valid key attends uniformly in the forward, as HF does (ctx = the mean of its V rows; its lse is finite
+ * and otherwise unspecified). Its backward is defined for dctx = 0 only -- what an encoder always feeds it: pooling gives such
+ * a sequence a zero embedding and a zero gradient -- and then every dqkv row of it is exactly 0. With a non-zero dctx the
+ * kernels return finite values that need not equal HF's gradient: the backward kernels mask with finfo.min / -inf against
+ * the forward's finite log2-domain constant, so they see probabilities 0 where the forward used 1 / L.
+ * (tests/test_gpu_attention_masks.py) */
 int qst_attention_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int64_t* mask,
                       const float* rel_bias, int nseq, int L, int A, int d, void* dqkv, float* drel,
                       float* delta_scratch, void* stream);

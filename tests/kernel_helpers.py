@@ -2,19 +2,18 @@
 
   * plumbing: the `lib` and `op` fixtures (`from kernel_helpers import lib, op  # noqa: F401`), stream / ptr, the operand
     types (OPDT, opr, kf) and the ctypes argument structs filled from keywords (gemm_args, ln_epi, ffn_args, attn_desc);
-  * references and layouts more than one file compares against: attn_ref, the dropout state / descriptor, the MX scale
-    layout (stage_major, row_major);
+  * references and layouts more than one file compares against: attn_ref (re-exported from attention_mask_cases, which the
+    host test imports without the library), the dropout state / descriptor, the MX scale layout (stage_major, row_major);
   * the encoder harness: quad_batch and run_step, one training forward + quadruplet loss + backward of a fresh HipEncoder.
 
 The rule: a helper lives in the test file that uses it; its second user moves it here instead of copying it. What a test
 asserts stays in its own file. tests/test_kernel_coverage_host.py reads the test files, not this module: an entry point is
 called by name (`lib.NAME`, `kf(lib, "NAME", op)`) from a test, never only from here.
 """
-import math
-
 import pytest
 import torch
 
+from attention_mask_cases import attn_ref  # noqa: F401  (moved there with its second user, the host test: re-exported)
 from oracle import dropout_ref as D
 from quadruplet_sentence_transformer_amd import _lib
 from quadruplet_sentence_transformer_amd.encoder import HipEncoder, quadruplet_loss_raw, stacked
@@ -80,21 +79,6 @@ def attn_desc(**kw):
 
 
 # ------------------------------------------------------------------ references
-def attn_ref(qkv, mask, rel, n, L, A, d, pm=None):
-    """HF attention (modeling_bert.py BertSelfAttention; MPNet adds the position bias `rel` [A, L, L] before the mask) in the
-    dtype of qkv, fp32 or fp64; pm [n, A, L, L]: dropout multipliers of the probabilities."""
-    H = A * d
-    q, k, v = [t.view(n, L, A, d).transpose(1, 2) for t in qkv.view(n, L, 3 * H).split(H, dim=-1)]
-    s = q @ k.transpose(-1, -2) / math.sqrt(d)
-    if rel is not None:
-        s = s + rel[None]
-    s = s + (1.0 - mask[:, None, None, :].to(qkv.dtype)) * torch.finfo(torch.float32).min
-    p = torch.softmax(s, -1)
-    if pm is not None:
-        p = p * pm
-    return (p @ v).transpose(1, 2).reshape(n * L, H)
-
-
 def drop_state(lib, seed, step):
     """The four-word dropout state of `seed` after `step` advances, built by the library's own init / advance launches."""
     st = torch.zeros(4, dtype=torch.int32, device="cuda")
