@@ -1,4 +1,5 @@
 from quadruplet_sentence_transformer_amd.evaluation import (EmbeddingSimilarityEvaluator,  # noqa: F401
-                                                            InformationRetrievalEvaluator,
-                                                            SentenceEvaluator, SequentialEvaluator,
-                                                            SimilarityFunction, TripletEvaluator)
+                                                            InformationRetrievalEvaluator, QuadrupletEvaluator,
+                                                            QuadrupletLossEvaluator, SentenceEvaluator,
+                                                            SequentialEvaluator, SimilarityFunction, TripletEvaluator,
+                                                            get_sequential_evaluator)

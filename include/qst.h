@@ -268,6 +268,19 @@ int qst_pair_loss(const float* u, const float* v, const float* labels, int B, in
 int qst_triplet_loss(const float* xa, const float* xp, const float* xn, int B, int D, int metric, float margin,
                      int reduction, float* out_loss, const float* grad_out,
                      float* grad_a, float* grad_p, float* grad_n, float* scratch, void* stream);
+/* What QuadrupletEvaluator scores with: per row the distances of (a, p), (a, q), (a, n) under three metrics and the three
+ * strict comparisons of each, from one pass over the four rows. Index k = 3 * metric + j with metric 0 = cosine distance
+ * (QST_METRIC_COS_DIST), 1 = Manhattan (QST_METRIC_L1_PLAIN), 2 = Euclidean (QST_METRIC_L2_PLAIN).
+ *   out_dist   fp32 [B, 9] or NULL: j = the pair, 0 (a, p), 1 (a, q), 2 (a, n)
+ *   out_flags  int32 [B]: bit k set = comparison j of the metric holds, j = 0 pos_part d(a, p) < d(a, q),
+ *              1 pos_neg d(a, p) < d(a, n), 2 part_neg d(a, q) < d(a, n)
+ *   out_counts int32 [9]: rows with bit k set; written, not accumulated (a fixed one-workgroup second stage over out_flags)
+ * The comparisons are made on the fp32 values out_dist receives, with or without out_dist. The three pairs of a metric go
+ * through one instruction sequence: bitwise-equal columns give bitwise-equal distances and a clear bit. Inputs fp32 [B, D],
+ * rows contiguous; any B >= 1 and D >= 1 (16-byte loads when D % 4 == 0 and the four pointers are 16-byte aligned).
+ * B < 1, D < 1 or a NULL input, out_flags or out_counts: QST_ERR_BAD_ARG, nothing written. */
+int qst_quadruplet_eval(const float* xa, const float* xp, const float* xq, const float* xn, int B, int D,
+                        float* out_dist, int32_t* out_flags, int32_t* out_counts, void* stream);
 
 /*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_grad_norm) + torch.optim.AdamW.step()

@@ -57,11 +57,19 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 }
 
 // metric class: 0 = products (cosine, dot), 1 = L2 of the difference, 2 = L1 of the difference (summed in fp64 into sd)
-template <int MC>
+// EXACT: every product-and-add is an explicit fma, so the compiler has no choice between fused and unfused forms (left to
+// itself it packs two pairs of a tuple into v_pk_fma_f32 and gives the third v_mul + v_add: equal inputs, unequal sums).
+// The losses keep EXACT = false and with it the bits they have always produced.
+template <int MC, bool EXACT = false>
 __device__ __forceinline__ void accum(float x, float y, float eps, float (&s)[3], double& sd) {
-    if (MC == 0) { s[0] += x * y; s[1] += x * x; s[2] += y * y; }
-    else if (MC == 1) { const float t = x - y + eps; s[0] += t * t; }
-    else sd += fabs((double)x - (double)y + (double)eps);
+    if (MC == 0) {
+        if (EXACT) { s[0] = __builtin_fmaf(x, y, s[0]); s[1] = __builtin_fmaf(x, x, s[1]); s[2] = __builtin_fmaf(y, y, s[2]); }
+        else { s[0] += x * y; s[1] += x * x; s[2] += y * y; }
+    } else if (MC == 1) {
+        const float t = x - y + eps;
+        if (EXACT) s[0] = __builtin_fmaf(t, t, s[0]);
+        else s[0] += t * t;
+    } else sd += fabs((double)x - (double)y + (double)eps);
 }
 
 // value m of a pair and the scalars of its gradient: MC 0: dm/dx = kxy*y + kxx*x, dm/dy = kxy*x + kyy*y;
@@ -70,7 +78,9 @@ __device__ __forceinline__ void accum(float x, float y, float eps, float (&s)[3]
 // md: m before its rounding to fp32 (MC 2), for the hinges
 struct PairVal { float m, kxy, kxx, kyy; double md; };
 
-template <int MC>
+// EXACT (value only, cosine similarity or distance): the same formula with contraction off, one IEEE operation per
+// operator, for the reason given at accum
+template <int MC, bool EXACT = false>
 __device__ __forceinline__ PairVal finish(const float (&s)[3], double sd, int metric) {
     PairVal r = {0.f, 0.f, 0.f, 0.f, 0.0};
     if (MC == 0) {
@@ -78,6 +88,15 @@ __device__ __forceinline__ PairVal finish(const float (&s)[3], double sd, int me
         if (metric == QST_METRIC_DOT) { r.m = dot; r.kxy = 1.f; r.md = (double)dot; return r; }
         const float nx = sqrtf(wave_sum(s[1])), ny = sqrtf(wave_sum(s[2]));
         const float cx = fmaxf(nx, kCosEps), cy = fmaxf(ny, kCosEps);
+        if (EXACT) {
+#pragma clang fp contract(off)
+            const float den = cx * cy;
+            const float inv = 1.f / den;
+            const float cs = dot * inv;
+            r.m = (metric == QST_METRIC_COS_DIST) ? 1.f - cs : cs;
+            r.md = (double)r.m;
+            return r;
+        }
         const float inv = 1.f / (cx * cy);
         const float cs = dot * inv;
         const float sg = (metric == QST_METRIC_COS_DIST) ? -1.f : 1.f;
@@ -328,6 +347,115 @@ bool distance_metric(int metric) {
     return metric == QST_METRIC_COS_DIST || metric == QST_METRIC_L2 || metric == QST_METRIC_L1;
 }
 
+// ---- quadruplet evaluation: the nine distances of a row (cosine, Manhattan, Euclidean of (a, p), (a, q), (a, n)) and the nine
+// strict comparisons QuadrupletEvaluator counts, from ONE pass over the four rows. No gradient pass, so nothing is kept in
+// registers and D is not bounded: the loops stream. All three metric classes accumulate side by side from the same loads; the
+// three pairs of a metric run the same accum / finish sequence in its EXACT form (explicit fma, no contraction left to the
+// compiler), so bitwise-equal columns give bitwise-equal distances.
+struct QuadEvalArgs {
+    const float* x[4];              // anchor, positive, partially positive, negative
+    float* dist;                    // [B, 9] or null
+    int32_t* flags;                 // [B]
+    int B, D;
+};
+
+struct QuadAcc {
+    float c[3][3], e[3][3];         // per pair: the cosine sums; the squared L2 sum in e[p][0]
+    double m[3];                    // per pair: the L1 sum
+};
+
+__device__ __forceinline__ void quad_accum(QuadAcc& q, float x0, float x1, float x2, float x3) {
+    const float y[3] = {x1, x2, x3};
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        double unused_d = 0.0;
+        accum<0, true>(x0, y[p], 0.f, q.c[p], unused_d);
+        accum<1, true>(x0, y[p], 0.f, q.e[p], unused_d);
+        accum<2, true>(x0, y[p], 0.f, q.e[p], q.m[p]);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void quad_eval_kernel(QuadEvalArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.B) return;
+    const int D = a.D;
+    const size_t base = (size_t)row * D;
+    const float* xa = a.x[0] + base;
+    const float* xp = a.x[1] + base;
+    const float* xq = a.x[2] + base;
+    const float* xn = a.x[3] + base;
+
+    QuadAcc q;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        q.m[p] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { q.c[p][k] = 0.f; q.e[p][k] = 0.f; }
+    }
+    if (VEC) {
+        const int nv = D >> 2;
+        for (int v = lane; v < nv; v += 64) {
+            const f32x4 A = *(const f32x4*)(xa + v * 4), P = *(const f32x4*)(xp + v * 4);
+            const f32x4 Q = *(const f32x4*)(xq + v * 4), N = *(const f32x4*)(xn + v * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) quad_accum(q, A[j], P[j], Q[j], N[j]);
+        }
+    } else {
+        for (int i = lane; i < D; i += 64) quad_accum(q, xa[i], xp[i], xq[i], xn[i]);
+    }
+
+    // d[3 * metric + pair]: what out_dist receives, and what is compared whether or not it is stored
+    float d[9];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        d[p] = finish<0, true>(q.c[p], 0.0, QST_METRIC_COS_DIST).m;
+        d[3 + p] = finish<2, true>(q.e[p], q.m[p], QST_METRIC_L1_PLAIN).m;
+        d[6 + p] = finish<1, true>(q.e[p], 0.0, QST_METRIC_L2_PLAIN).m;
+    }
+    int32_t f = 0;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        f |= (d[3 * m] < d[3 * m + 1] ? 1 : 0) << (3 * m);          // pos_part
+        f |= (d[3 * m] < d[3 * m + 2] ? 1 : 0) << (3 * m + 1);      // pos_neg
+        f |= (d[3 * m + 1] < d[3 * m + 2] ? 1 : 0) << (3 * m + 2);  // part_neg
+    }
+    if (lane == 0) {
+        a.flags[row] = f;
+        if (a.dist) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) a.dist[(size_t)row * 9 + k] = d[k];
+        }
+    }
+}
+
+// counts[k] = number of rows whose bit k is set. One workgroup; integer sums, so the order cannot matter. Every wave walks the
+// rows in whole trips of 1024 (its lanes past B hold 0), which keeps the ballots wave-uniform.
+__global__ __launch_bounds__(1024) void quad_count_kernel(const int32_t* flags, int B, int32_t* counts) {
+    __shared__ int32_t part[16][9];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t c[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c[k] = 0;
+    for (int64_t i0 = 0; i0 < B; i0 += 1024) {  // 64-bit: the last trip's indices pass B, and B may be near INT_MAX
+        const int64_t i = i0 + threadIdx.x;
+        const int32_t f = (i < B) ? flags[i] : 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) c[k] += (int32_t)__popcll(__ballot((f >> k) & 1));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) part[wave][k] = c[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {
+        int32_t s = 0;
+        for (int w = 0; w < 16; ++w) s += part[w][threadIdx.x];
+        counts[threadIdx.x] = s;
+    }
+}
+
 }  // namespace
 
 extern "C" int qst_pair_metric(const float* u, const float* v, int B, int D, int metric, float* out,
@@ -414,5 +542,24 @@ extern "C" int qst_triplet_loss(const float* xa, const float* xp, const float* x
         tuple_reduce_kernel<<<1, 1024, 0, st>>>(scratch, B, reduction == QST_REDUCE_MEAN ? 1.0f / (float)B : 1.0f, out_loss);
         QST_LAUNCH_CHECK();
     }
+    return QST_OK;
+}
+
+extern "C" int qst_quadruplet_eval(const float* xa, const float* xp, const float* xq, const float* xn, int B, int D,
+                                   float* out_dist, int32_t* out_flags, int32_t* out_counts, void* stream) {
+    if (!xa || !xp || !xq || !xn || !out_flags || !out_counts || B < 1 || D < 1) return QST_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    QuadEvalArgs a = {};
+    a.x[0] = xa; a.x[1] = xp; a.x[2] = xq; a.x[3] = xn;
+    a.dist = out_dist; a.flags = out_flags; a.B = B; a.D = D;
+    bool vec = D % 4 == 0;
+    for (int k = 0; k < 4; ++k) vec = vec && ((uintptr_t)a.x[k] & 15) == 0;
+    const int grid = (int)(((int64_t)B + 3) / 4);
+    if (vec) quad_eval_kernel<true><<<grid, 256, 0, st>>>(a);
+    else quad_eval_kernel<false><<<grid, 256, 0, st>>>(a);
+    QST_LAUNCH_CHECK();
+    // second stage: one workgroup over the flags, in stream order behind the first
+    quad_count_kernel<<<1, 1024, 0, st>>>(out_flags, B, out_counts);
+    QST_LAUNCH_CHECK();
     return QST_OK;
 }

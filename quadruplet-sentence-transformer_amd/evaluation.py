@@ -1,11 +1,16 @@
 """sentence_transformers.evaluation surface used by the reference's evaluators (models/evaluators.py:9-12,187-216,
 572-612; ir_evauation_script.py:107-131): the base class, SimilarityFunction, SequentialEvaluator, an encode()-driven
 TripletEvaluator and InformationRetrievalEvaluator, whose scoring + top-k run on the GPU
-through libqst (util.topk_scores), and EmbeddingSimilarityEvaluator (graded pairs; qst_pair_metric)."""
+through libqst (util.topk_scores), and EmbeddingSimilarityEvaluator (graded pairs; qst_pair_metric). The two evaluators the
+reference selects its models with, QuadrupletEvaluator (qst_quadruplet_eval) and QuadrupletLossEvaluator, and the chain
+get_sequential_evaluator builds of them stand at the end."""
 from __future__ import annotations
 
 import csv
+import json
+import logging
 import os
+import random
 from enum import Enum
 from typing import Callable, Dict, Iterable, List, Optional, Set
 
@@ -374,3 +379,247 @@ class InformationRetrievalEvaluator(SentenceEvaluator):
             out[nm] = ir_metrics(results, self.queries_ids, self.relevant_docs, self.mrr_at_k, self.ndcg_at_k,
                                  self.accuracy_at_k, self.precision_recall_at_k, self.map_at_k)
         return out
+
+
+# ------------------------------------------------------------------ the quadruplet evaluators
+LOGGER = logging.getLogger(__name__)
+
+
+def _append_csv(path: str, headers: List[str], row: list) -> None:
+    new = not os.path.isfile(path)
+    with open(path, "a", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        if new:
+            w.writerow(headers)
+        w.writerow(row)
+
+
+def _unwrap_example(example):
+    """An (example, label) row gives its example."""
+    return example[0] if isinstance(example, tuple) else example
+
+
+def sample_quadruplets(examples):
+    """(anchors, positives, partially positives, negatives) of rows that are objects with four `texts`, (example, label)
+    tuples, or quadruplet dicts (quadruplet_model's keys); where a dict holds a list, one entry is drawn with `random`
+    (positive, then partially positive, then negative: one draw each, in that order)."""
+    from .quadruplet_model import NEG_EXAMPLES, PART_POS_EXAMPLES, POS_EXAMPLES, REFERENCE_EXAMPLE
+    cols = ([], [], [], [])
+    for example in examples:
+        example = _unwrap_example(example)
+        if hasattr(example, "texts"):
+            if len(example.texts) < 4:
+                raise ValueError(f"a quadruplet example needs four texts, {len(example.texts)} given")
+            for col, text in zip(cols, example.texts[:4]):
+                col.append(text)
+            continue
+        cols[0].append(example[REFERENCE_EXAMPLE])
+        for col, key in zip(cols[1:], (POS_EXAMPLES, PART_POS_EXAMPLES, NEG_EXAMPLES)):
+            v = example[key]
+            col.append(v[random.randint(0, len(v) - 1)] if isinstance(v, list) else v)
+    return cols
+
+
+class QuadrupletEvaluator(SentenceEvaluator):
+    """Quadruplets (sentence, positive, partially positive, negative): the accuracies of
+        pos_part  d(sentence, positive) < d(sentence, partially positive)
+        pos_neg   d(sentence, positive) < d(sentence, negative)
+        part_neg  d(sentence, partially positive) < d(sentence, negative)
+    each under cosine, Manhattan and Euclidean distance, and the score
+        ((1 - gamma) * pos_part + gamma * part_neg + pos_neg) / 2,
+    where each of the three is the accuracy `main_distance_function` names, or the largest of its three when that is None
+    (TripletEvaluator's rule). Constructor, attributes, CSV files and return value are the reference's, which composes the
+    score from three TripletEvaluators: nine encodes of four distinct lists, and nine distances per row in host numpy. Here
+    every list is encoded once, the embeddings stay on the device, and ONE qst_quadruplet_eval launch returns the nine
+    counts -- all that comes back to the host.
+
+    With `all_examples` (from_input_examples keeps its argument there) the four lists are drawn again on every fifth call."""
+
+    N_EPOCHS_RESET_EXAMPLES = 5
+    _TRIPLETS = ("pos_part", "pos_neg", "part_neg")
+
+    def __init__(self, anchors: List[str], positives: List[str], partially_positives: List[str], negatives: List[str],
+                 gamma: float = 0.6, main_distance_function: Optional[SimilarityFunction] = None, name: str = "",
+                 batch_size: int = 16, show_progress_bar: bool = False, write_csv: bool = True, all_examples=None):
+        self.anchors, self.positives = anchors, positives
+        self.partially_positives, self.negatives = partially_positives, negatives
+        self.name = name
+        self._gamma = gamma
+        self._all_examples = all_examples
+        assert len(self.anchors) == len(self.positives)
+        assert len(self.anchors) == len(self.partially_positives)
+        assert len(self.anchors) == len(self.negatives)
+        self.main_distance_function = main_distance_function
+        self.batch_size = batch_size
+        if show_progress_bar is None:
+            show_progress_bar = LOGGER.getEffectiveLevel() in (logging.INFO, logging.DEBUG)
+        self.show_progress_bar = show_progress_bar
+        self.write_csv = write_csv
+        self.csv_file = "quadruplet_evaluation" + ("_" + name if name else "") + "_results.csv"
+        self.csv_headers = ["epoch", "steps", "pos_part_accuracy", "pos_neg_accuracy", "part_neg_accuracy", "global_accuracy"]
+        # the per-triplet files the reference's three TripletEvaluators (named pos_part, pos_neg, part_neg) leave
+        self.triplet_csv_files = [f"triplet_evaluation_{t}_results.csv" for t in self._TRIPLETS]
+        self.triplet_csv_headers = ["epoch", "steps", "accuracy_cosinus", "accuracy_manhattan", "accuracy_euclidean"]
+        self._epoch_counter = 0
+
+    @classmethod
+    def from_input_examples(cls, examples, **kwargs):
+        return cls(*sample_quadruplets(examples), all_examples=examples, **kwargs)
+
+    def _reset_examples(self) -> None:
+        self._epoch_counter += 1
+        if self._all_examples is not None and self._epoch_counter % self.N_EPOCHS_RESET_EXAMPLES == 0:
+            self.anchors, self.positives, self.partially_positives, self.negatives = sample_quadruplets(self._all_examples)
+
+    def quadruplet_counts(self, model):
+        """The device step: (counts[9], N) with counts[3 * metric + j] = rows on which comparison j (pos_part, pos_neg,
+        part_neg) holds under metric 0 cosine, 1 Manhattan, 2 Euclidean. Four encodes, one launch, nine integers back."""
+        import torch
+        from . import st_losses as S
+        embs = [model.encode(xs, batch_size=self.batch_size, show_progress_bar=self.show_progress_bar, convert_to_tensor=True)
+                for xs in (self.anchors, self.positives, self.partially_positives, self.negatives)]
+        with torch.no_grad():
+            _, _, counts = S.quadruplet_eval(*embs)
+        return counts.cpu().numpy().astype(np.int64), len(self.anchors)
+
+    def _main_accuracy(self, acc_cos: float, acc_man: float, acc_euc: float) -> float:
+        if self.main_distance_function == SimilarityFunction.COSINE:
+            return acc_cos
+        if self.main_distance_function == SimilarityFunction.MANHATTAN:
+            return acc_man
+        if self.main_distance_function == SimilarityFunction.EUCLIDEAN:
+            return acc_euc
+        return max(acc_cos, acc_man, acc_euc)
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1) -> float:
+        self._reset_examples()
+        LOGGER.info("QuadrupletEvaluator %s: epoch %d, steps %d", self.name, epoch, steps)
+        counts, n = self.quadruplet_counts(model)
+        counts = np.asarray(counts, dtype=np.float64).reshape(3, 3)      # [metric, comparison]
+        write = output_path is not None and self.write_csv
+        main = []
+        for j, fname in enumerate(self.triplet_csv_files):
+            acc = [float(counts[m, j] / n) for m in range(3)]            # cosine, Manhattan, Euclidean: the CSV's columns
+            if write:
+                _append_csv(os.path.join(output_path, fname), self.triplet_csv_headers, [epoch, steps, *acc])
+            main.append(self._main_accuracy(*acc))
+        pos_part, pos_neg, part_neg = main
+        glob = ((1 - self._gamma) * pos_part + self._gamma * part_neg + pos_neg) / 2
+        LOGGER.info("accuracy %%: pos_part %.2f, pos_neg %.2f, part_neg %.2f, global %.2f", pos_part * 100, pos_neg * 100,
+                    part_neg * 100, glob * 100)
+        if write:
+            _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers,
+                        [epoch, steps, pos_part, pos_neg, part_neg, glob])
+        return glob
+
+
+class QuadrupletLossEvaluator(SentenceEvaluator):
+    """The mean quadruplet loss over a dataset, batch by batch, under torch.no_grad(): the running mean
+    avg += (loss - avg) / (i + 1) of QuadrupletSentenceTransformerLossModel(model, quadruplet_loss) (one fused encoder pass
+    per batch) over an unshuffled DataLoader. The mean stays a device tensor; the host waits for it once, at the end, to log
+    it. Rows are InputExamples with four texts, (example, label) tuples, or quadruplet dicts (to_input_example).
+
+    The model's mode is left as it is: inside fit() the model is in train() mode, so this loss is taken with dropout, as the
+    reference takes it (SentenceTransformer.forward supports exactly that pass); call model.eval() first for a
+    deterministic figure.
+
+    With output_path, epoch / steps / average_loss are appended to <output_path>/_quadruplet_loss_eval.json. With
+    output_path=None nothing is written and the loss is returned (the reference raises there, joining None with the file
+    name).
+
+    use_amp is accepted and stored for the reference's signature. There is no autocast on this path: the pass runs at the
+    precision the model's forward is using, which inside fit(use_amp=True) already is f16.
+
+    Returns the mean as a 0-d tensor on the model's device (the reference returns its tensor too)."""
+
+    LOG_FILE = "_quadruplet_loss_eval.json"
+
+    def __init__(self, quadruplet_dataset, quadruplet_loss, batch_size: int = 32,
+                 additional_model_kwargs: Optional[List[str]] = None, additional_loss_kwargs: Optional[List[str]] = None,
+                 use_amp: bool = False):
+        self._quadruplet_dataset = quadruplet_dataset
+        self._quadruplet_loss = quadruplet_loss
+        self._batch_size = batch_size
+        self._additional_model_kwargs = additional_model_kwargs
+        self._additional_loss_kwargs = additional_loss_kwargs
+        self._use_amp = use_amp
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1):
+        import torch
+        from torch.utils.data import DataLoader
+        from .quadruplet_model import QuadrupletSentenceTransformerLossModel, to_input_example
+        from .sentence_transformer import batch_to_device
+        loss_model = QuadrupletSentenceTransformerLossModel(
+            st_model=model, quadruplet_loss=self._quadruplet_loss, additional_model_kwargs=self._additional_model_kwargs,
+            additional_loss_kwargs=self._additional_loss_kwargs)
+
+        def collate(batch):
+            rows = [_unwrap_example(b) for b in batch]
+            return model.smart_batching_collate([r if hasattr(r, "texts") else to_input_example(r) for r in rows])
+
+        loader = DataLoader(self._quadruplet_dataset, batch_size=self._batch_size, shuffle=False, collate_fn=collate)
+        avg = torch.zeros((), dtype=torch.float32, device=model.device)
+        with torch.no_grad():
+            for i, (features, labels) in enumerate(loader):
+                features = [batch_to_device(f, model.device) for f in features]
+                loss_value = loss_model(features, labels.to(model.device))
+                avg += (loss_value.detach().to(torch.float32).mean() - avg) / (i + 1)
+        if output_path is not None:
+            path = os.path.join(output_path, self.LOG_FILE)
+            log = {}
+            if os.path.exists(path):
+                with open(path, "r") as fp:
+                    log = json.load(fp)
+            for k, v in (("epoch", epoch), ("steps", steps), ("average_loss", avg.item())):
+                log.setdefault(k, []).append(v)
+            with open(path, "w") as fp:
+                json.dump(log, fp, indent=2)
+        return avg
+
+
+def get_sequential_evaluator(dataset, loss, evaluation_queries_path: Optional[str] = None, no_transform_dataset=None,
+                             corpus_chunk_size: int = 50000, mrr_at_k: List[int] = [10], ndcg_at_k: List[int] = [10],
+                             accuracy_at_k: List[int] = [1, 3, 5, 10], precision_recall_at_k: List[int] = [1, 3, 5, 10],
+                             map_at_k: List[int] = [100], show_progress_bar: bool = False, batch_size: int = 32,
+                             write_csv: bool = True, score_functions: Optional[Dict[str, Callable]] = None,
+                             main_score_function: Optional[str] = None,
+                             main_distance_function: Optional[SimilarityFunction] = None, name: str = "",
+                             additional_model_kwargs: Optional[List[str]] = None,
+                             additional_loss_kwargs: Optional[List[str]] = None, use_amp: bool = False) -> SequentialEvaluator:
+    """SequentialEvaluator([InformationRetrievalEvaluator?, QuadrupletEvaluator, QuadrupletLossEvaluator]) over `dataset`
+    with `loss` (its gamma weights the accuracy): the loss evaluator is last, so its value is the chain's score.
+
+    The retrieval evaluator is built only from `evaluation_queries_path`, a JSON file {"queries": {qid: text}, "corpus":
+    {cid: text}, "relevant": {qid: [cid, ...]}}. score_functions=None stands for {'cos_sim', 'dot_score'}, the two this
+    package scores natively. Building the query set from `no_transform_dataset` (the reference's create_ir_evaluation_set:
+    a cross-encoder scores a sampled corpus) is not done here: with that argument and no readable file the call raises."""
+    evaluation_queries = None
+    if evaluation_queries_path is not None:
+        try:
+            with open(evaluation_queries_path, "r") as fp:
+                evaluation_queries = json.load(fp)
+            # The evaluator takes a set per query. (The reference converts the whole `relevant` mapping -- its keys, the query
+            # ids -- for every query instead of the query's own list; each query gets its own list here.)
+            evaluation_queries["relevant"] = {q: set(docs) for q, docs in evaluation_queries["relevant"].items()}
+        except IOError as e:
+            evaluation_queries = None
+            print(f"Error: {evaluation_queries_path} file could not be opened due to error: {e}")
+    if evaluation_queries is None and no_transform_dataset is not None:
+        raise NotImplementedError("get_sequential_evaluator: no readable evaluation_queries_path, and building the retrieval "
+                                  "set from no_transform_dataset (create_ir_evaluation_set: cross-encoder scoring of a "
+                                  "sampled corpus) is not implemented; write the queries file first")
+    evaluators = []
+    if evaluation_queries is not None:
+        evaluators.append(InformationRetrievalEvaluator(
+            queries=evaluation_queries["queries"], corpus=evaluation_queries["corpus"],
+            relevant_docs=evaluation_queries["relevant"], corpus_chunk_size=corpus_chunk_size, mrr_at_k=mrr_at_k,
+            ndcg_at_k=ndcg_at_k, accuracy_at_k=accuracy_at_k, precision_recall_at_k=precision_recall_at_k, map_at_k=map_at_k,
+            show_progress_bar=show_progress_bar, batch_size=batch_size, name=name, write_csv=write_csv,
+            score_functions=score_functions, main_score_function=main_score_function))
+    evaluators.append(QuadrupletEvaluator.from_input_examples(
+        dataset, gamma=loss.gamma, main_distance_function=main_distance_function, name=name, batch_size=batch_size,
+        show_progress_bar=show_progress_bar, write_csv=write_csv))
+    evaluators.append(QuadrupletLossEvaluator(
+        quadruplet_dataset=dataset, quadruplet_loss=loss, additional_model_kwargs=additional_model_kwargs,
+        additional_loss_kwargs=additional_loss_kwargs, use_amp=use_amp, batch_size=batch_size))
+    return SequentialEvaluator(evaluators=evaluators)

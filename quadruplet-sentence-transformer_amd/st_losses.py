@@ -174,6 +174,34 @@ def triplet_loss(anchor, pos, neg, metric: int = METRIC_L2, margin: float = 5.0,
     return _TripletLossFn.apply(anchor, pos, neg, int(metric), float(margin), _RED_CODE[reduction])
 
 
+def quadruplet_eval_raw(a, p, q, n, want_dist: bool = False):
+    """qst_quadruplet_eval on contiguous fp32 HIP tensors [B, D] (contiguous in their own storage: a view at an offset
+    is taken as it is): (dist fp32 [B, 9] or None, flags int32 [B], counts int32 [9])."""
+    lib = _lib.load()
+    B, D = a.shape
+    dist = torch.empty(B, 9, dtype=torch.float32, device=a.device) if want_dist else None
+    flags = torch.empty(B, dtype=torch.int32, device=a.device)
+    counts = torch.empty(9, dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.qst_quadruplet_eval(a.data_ptr(), p.data_ptr(), q.data_ptr(), n.data_ptr(), B, D, _lib.ptr(dist),
+                                           flags.data_ptr(), counts.data_ptr(), _lib.current_stream_ptr()),
+                   "qst_quadruplet_eval")
+    return dist, flags, counts
+
+
+def quadruplet_eval(a, p, q, n, want_dist: bool = False):
+    """What QuadrupletEvaluator scores with, in one launch over four [B, D] HIP tensors (anchor, positive, partially
+    positive, negative): index k = 3 * metric + j, metric 0 cosine distance, 1 Manhattan, 2 Euclidean.
+      dist   fp32 [B, 9] (None without want_dist): j = the pair (a, p), (a, q), (a, n)
+      flags  int32 [B]: bit k = comparison j holds, j = 0 d(a, p) < d(a, q), 1 d(a, p) < d(a, n), 2 d(a, q) < d(a, n)
+      counts int32 [9]: rows with bit k set
+    Every comparison is strict and made on the fp32 distances `dist` holds. No autograd."""
+    _require_rows("quadruplet_eval", a, p, q, n)
+    if a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("quadruplet_eval: the embeddings must have at least one row and one column")
+    return quadruplet_eval_raw(*_f32((a, p, q, n)), want_dist=want_dist)
+
+
 # ------------------------------------------------------------------ the metric classes
 def _tagged(metric: int, doc: str):
     def fn(x, y):
