@@ -115,7 +115,14 @@ int qst_gemm_nt_ln_block_rows_m(int N, int M);   /* ... exactly: above N = 384 t
 int qst_gemm_nt_ln(const QstGemmArgs* a, const QstLnEpi* ln, int mode, void* stream);
 /* The same with rows wider than one tile, N = 512 / 768 / 1024 (csrc/gemm8.hip: 256 x 256 tiles on the 8-phase loop, the
  * N / 256 workgroups of a 256-row panel exchange the row statistics inside the launch); qst_gemm_nt_ln forwards here.
- * partials f32 [ceil(M / qst_gemm_nt8_ln_block_rows(M, N))][2][N]; no B2. qst_gemm_nt8_ln_timeouts(): 0 unless an exchange of this process ever gave up. */
+ * partials f32 [ceil(M / qst_gemm_nt8_ln_block_rows(M, N))][2][N]; no B2. qst_gemm_nt8_ln_timeouts(): 0 unless an exchange of this process ever gave up.
+ * Host state (process-wide): the exchange runs on one buffer per (device, stream), allocated by that stream's first eager
+ * launch (16 MiB at least), sixteen at most per process -- the _f16 twin has sixteen, and a timeout word, of its own;
+ * qst_gemm_nt8_f8_ln shares this table -- and never released: the launch on a 17th pair returns QST_ERR_UNSUPPORTED. A launch
+ * that outgrows its buffer gets a larger one; the old one is kept, a captured graph may hold its address. While its stream is
+ * capturing a launch cannot allocate: without a large enough buffer of its own it takes the smallest one of the device that
+ * fits, so a capture needs an earlier eager launch of at least that size on the device (QST_ERR_UNSUPPORTED otherwise; nothing
+ * is recorded), and a graph must not run side by side with eager launches, or another graph, on the buffer it borrowed. */
 int qst_gemm_nt8_ln_supported(int N);
 int qst_gemm_nt8_ln_block_rows(int M, int N);   /* 256, or 128 where the 128 x 384 tile is taken (N = 768, 32,768 <= M < 43,691) */
 int qst_gemm_nt8_ln(const QstGemmArgs* a, const QstLnEpi* ln, int mode, void* stream);

@@ -938,8 +938,13 @@ static int lnx_get(hipStream_t st, size_t bytes, LnXchg& x) {
     const bool capturing = cap != hipStreamCaptureStatusNone;
     if (!g_lnx_tmo[dev]) {
         if (capturing) return QST_ERR_UNSUPPORTED;       // no eager launch on this device before the capture
-        QST_HIP_CHECK(hipMalloc((void**)&g_lnx_tmo[dev], 256));
-        QST_HIP_CHECK(hipMemset(g_lnx_tmo[dev], 0, 256));
+        // (zeroed ON `st` and waited for: hipMemset runs on the null stream, which a non-blocking stream -- every stream torch
+        //  hands out -- is not ordered with, so the launch that follows could run before, or under, the zeroing)
+        unsigned* t = nullptr;
+        QST_HIP_CHECK(hipMalloc((void**)&t, 256));
+        QST_HIP_CHECK(hipMemsetAsync(t, 0, 256, st));
+        QST_HIP_CHECK(hipStreamSynchronize(st));
+        g_lnx_tmo[dev] = t;
     }
     LnxBuf* b = nullptr;
     for (auto& q : g_lnx) if (q.used && q.dev == dev && q.st == st) { b = &q; break; }
@@ -957,7 +962,12 @@ static int lnx_get(hipStream_t st, size_t bytes, LnXchg& x) {
             const size_t want = bytes > kLnxMinBytes ? bytes : kLnxMinBytes;
             unsigned long long* p = nullptr;
             QST_HIP_CHECK(hipMalloc((void**)&p, want + 256));
-            QST_HIP_CHECK(hipMemset(p, 0, want + 256));  // epoch 0, no tag set; never zeroed again (tags carry the epoch)
+            // epoch 0, no tag set; never zeroed again (tags carry the epoch). Zeroed on `st` and waited for, once per buffer: on
+            // the null stream (hipMemset) the zeroing is not ordered with a launch on a non-blocking stream and wiped granules
+            // that the first launch had already published -- the partner tile then polled until its timeout. The wait also
+            // orders it before a graph on another stream that borrows this buffer later.
+            QST_HIP_CHECK(hipMemsetAsync(p, 0, want + 256, st));
+            QST_HIP_CHECK(hipStreamSynchronize(st));
             b->gran = p; b->bytes = want;
         }
     }

@@ -3,7 +3,8 @@
   * plumbing: the `lib` and `op` fixtures (`from kernel_helpers import lib, op  # noqa: F401`), stream / ptr, the operand
     types (OPDT, opr, kf) and the ctypes argument structs filled from keywords (gemm_args, ln_epi, ffn_args, attn_desc);
   * references and layouts more than one file compares against: attn_ref (re-exported from attention_mask_cases, which the
-    host test imports without the library), the dropout state / descriptor, the MX scale layout (stage_major, row_major);
+    host test imports without the library), the dropout state / descriptor, the MX scale layout (stage_major, row_major) and
+    the MXFP8 quantisation of an operand on the device (quant_dev);
   * the encoder harness: quad_batch and run_step, one training forward + quadruplet loss + backward of a fresh HipEncoder.
 
 The rule: a helper lives in the test file that uses it; its second user moves it here instead of copying it. What a test
@@ -105,6 +106,16 @@ def stage_major(s_rowmajor):
 def row_major(s_stage, rows, K):
     nb = K // 32
     return s_stage.view((nb + 3) // 4, rows, 4).permute(1, 0, 2).reshape(rows, -1)[:, :nb]
+
+
+def quant_dev(lib, x, bf16=False):
+    """x [rows, K] as MXFP8 on the device: the e4m3 elements and the stage-major scales qst_quant_mx writes."""
+    rows, K = x.shape
+    src = x.cuda().to(torch.bfloat16 if bf16 else torch.float32).contiguous()
+    q = torch.empty(rows, K, dtype=torch.uint8, device="cuda")
+    s = torch.zeros((K + 127) // 128 * rows * 4, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.qst_quant_mx(src.data_ptr(), int(bf16), rows, K, q.data_ptr(), s.data_ptr(), stream()))
+    return q, s
 
 
 # ------------------------------------------------------------------ encoder harness

@@ -12,16 +12,8 @@ pytestmark = pytest.mark.gpu
 import quadruplet_sentence_transformer_amd  # noqa: E402,F401
 from quadruplet_sentence_transformer_amd import _lib  # noqa: E402
 from oracle import torch_ref as R  # noqa: E402
-from kernel_helpers import gemm_args, lib, ln_epi, quad_batch, row_major, run_step, stage_major, stream  # noqa: E402,F401
-
-
-def quant_dev(lib, x, bf16=False):
-    rows, K = x.shape
-    src = x.cuda().to(torch.bfloat16 if bf16 else torch.float32).contiguous()
-    q = torch.empty(rows, K, dtype=torch.uint8, device="cuda")
-    s = torch.zeros((K + 127) // 128 * rows * 4, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.qst_quant_mx(src.data_ptr(), int(bf16), rows, K, q.data_ptr(), s.data_ptr(), stream()))
-    return q, s
+from kernel_helpers import (gemm_args, lib, ln_epi, quad_batch, quant_dev, row_major, run_step, stage_major,  # noqa: E402,F401
+                            stream)
 
 
 @pytest.mark.parametrize("rows,K", [(1, 32), (7, 96), (130, 768), (64, 3072)])
