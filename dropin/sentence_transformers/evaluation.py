@@ -1,5 +1,6 @@
 from quadruplet_sentence_transformer_amd.evaluation import (EmbeddingSimilarityEvaluator,  # noqa: F401
-                                                            InformationRetrievalEvaluator, QuadrupletEvaluator,
+                                                            InformationRetrievalEvaluator, ParaphraseMiningEvaluator,
+                                                            QuadrupletEvaluator,
                                                             QuadrupletLossEvaluator, SentenceEvaluator,
                                                             SequentialEvaluator, SimilarityFunction, TripletEvaluator,
                                                             get_sequential_evaluator)

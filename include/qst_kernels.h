@@ -384,6 +384,26 @@ int qst_dropout_apply_f32(const QstDrop* d, const float* in, const float* resid,
 int qst_topk_rows(const float* scores, int64_t ld, const int64_t* index_map, int nrows, int n, int k,
                   float* out_scores, int64_t* out_index, void* stream);
 
+/* Streaming top-k: the k best of a row's running result and one more chunk of its scores, so that a corpus of any
+ * size goes through in pieces and the answer is the same for every way of cutting it. scores f32 [nrows, ld] (first n
+ * columns; column j is global id col_base + j), run_scores f32 / run_index int64 [nrows, k]: the caller fills them with
+ * -inf / -1 (= empty) before the first chunk. Order: score descending (NaN above +inf), then id ascending -- also among
+ * the entries tied at the k-th place, whatever their number. exclude_self != 0 drops the candidate whose id is
+ * row_base + row; candidates above max_score do not take part (+inf: all do). Fewer than k candidates leave the tail
+ * -inf / -1. k <= 1024. An id must not reach a row twice (the same chunk merged again). */
+int qst_topk_merge_rows(const float* scores, int64_t ld, int nrows, int n, int64_t col_base, int64_t row_base,
+                        int exclude_self, float max_score, int k, float* run_scores, int64_t* run_index, void* stream);
+
+/* queries f32 [nq, dim] against corpus f32 [nc, dim] in chunks of `chunk` rows: prepare (qst.h: QST_SCORE_*), score
+ * (split-bf16 x3 GEMM or the Euclidean kernel), qst_topk_merge_rows. Global ids: query row r is query_base + r, corpus
+ * row c is corpus_base + c. May be called again with the next piece of a corpus that is not on the device at once:
+ * run_* carry the state. The workspace holds the prepared queries, one prepared chunk and one
+ * [min(nq, 2048), chunk] score block; one chunk's operand stays below 2^31 bytes, nc is any int. dim % 32 == 0. */
+size_t qst_topk_stream_workspace_bytes(int nq, int chunk, int dim);
+int qst_topk_stream(const float* queries, const float* corpus, int nq, int nc, int dim, int k, int mode, int chunk,
+                    int64_t query_base, int64_t corpus_base, int exclude_self, float max_score,
+                    float* run_scores, int64_t* run_index, void* workspace, size_t workspace_bytes, void* stream);
+
 /* All GEMM weights of the arena in one launch; table_dev = int64 [nseg][6] {src off, rows, cols, dst off, dstT off,
  * first block} (built by qst_encoder_create). */
 int qst_shadow_all(const float* params, void* shadow, const int64_t* table_dev, int nseg, int nblocks, void* stream);

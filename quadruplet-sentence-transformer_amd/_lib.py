@@ -191,6 +191,11 @@ SIGNATURES = {
     "qst_rel_pos_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     "qst_rel_pos_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "qst_topk_rows": (C.c_int, [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "qst_topk_merge_rows": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_int,
+                                      vp, vp, vp]),
+    "qst_topk_stream_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "qst_topk_stream": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                  C.c_int, C.c_float, vp, vp, vp, C.c_size_t, vp]),
     "qst_shadow_matrix": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
     "qst_shadow_all": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "qst_gemm_nt_x3": (C.c_int, [C.POINTER(QstGemmArgs), C.c_int, vp]),

@@ -9,6 +9,9 @@
 // Here: rows are normalised (cosine) or copied into a 4-row-padded workspace, the [nq, nc] score matrix comes from the
 // split-bf16 x3 GEMM (fp32-class products: near-ties keep the order an fp32 matmul would give them), and one
 // workgroup per query selects the k best by a 4-pass radix select on order-preserving integer keys, then sorts them.
+//
+// qst_topk_stream does the same chunk by chunk for a corpus of any size: each chunk's score block is merged into a
+// running [nq, k] result by topk_merge_kernel, whose ties are decided by global id, so the chunking does not show.
 #include "qst_common.h"
 #include "qst_kernels.h"
 
@@ -125,6 +128,136 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* scores, int
     }
 }
 
+__device__ __forceinline__ float fkey_inv(uint32_t key) {
+    return __builtin_bit_cast(float, (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
+// Merge one chunk's scores into a running top-k: one workgroup per row. The candidates are the n scores of the row (global
+// id col_base + column) and the k entries of run_* (index -1 = empty). A candidate takes part unless its id is negative,
+// is the row's own (exclude_self) or its score is above cap. The k best by (score descending, id ascending) go back to
+// run_*, real entries first, then -inf / -1.
+//
+// The order is one composite key, (fkey(score), ~id), and the radix select runs over all of it: four 8-bit passes over the
+// score key as in topk_rows_kernel, then passes over the id bytes from the top non-zero byte of the largest id down, with
+// the digit inverted so that the smaller id is the larger digit. It stops at the first pass whose chosen bin holds
+// exactly what is still needed -- for distinct scores at the cut that is pass 4 at the latest, so the id passes run only
+// when equal scores straddle the cut, and then they decide it by id however many the ties are. The chosen set therefore
+// does not depend on atomic arrival order or on how the columns were cut into chunks; the bitonic sort orders it.
+//
+// The old running row lives in registers (k <= 1024 = 4 per thread) from before the first barrier; run_* is written only
+// after the sort. LDS: 4 KB keys + 8 KB ids + the 1 KB histogram.
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* scores, int64_t ld, int n, int64_t col_base,
+                                                         int64_t row_base, int exclude_self, float cap, int k,
+                                                         float* run_scores, int64_t* run_index) {
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sh_digit, sh_need, sh_state, sh_cnt;
+    __shared__ unsigned long long sh_idmax;
+    __shared__ uint32_t sk[TOPK_MAX];
+    __shared__ int64_t si[TOPK_MAX];
+    const int tid = threadIdx.x;
+    const float* row = scores + (size_t)blockIdx.x * ld;
+    float* rs = run_scores + (size_t)blockIdx.x * k;
+    int64_t* rx = run_index + (size_t)blockIdx.x * k;
+    const int64_t self = exclude_self ? row_base + blockIdx.x : -1;     // -1: no id equals it (negative ids are empty)
+
+    float rv[4];
+    int64_t ri[4];
+    int64_t idmax = col_base + n - 1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int j = tid + 256 * e;
+        rv[e] = j < k ? rs[j] : -INFINITY;
+        ri[e] = j < k ? rx[j] : -1;
+        idmax = ri[e] > idmax ? ri[e] : idmax;
+    }
+    if (tid == 0) sh_idmax = 0;
+    __syncthreads();
+    atomicMax(&sh_idmax, (unsigned long long)idmax);
+    __syncthreads();
+    const int id_passes = (64 - __builtin_clzll(sh_idmax | 1ull) + 7) / 8;
+
+    // f(key, id) for every candidate of this thread that takes part
+    auto visit = [&](auto&& f) {
+        for (int i = tid; i < n; i += 256) {
+            const float v = row[i];
+            const int64_t id = col_base + i;
+            if (id != self && !(v > cap)) f(fkey(v), id);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (ri[e] >= 0 && ri[e] != self && !(rv[e] > cap)) f(fkey(rv[e]), ri[e]);
+    };
+
+    // after the passes: a candidate is taken iff (key & kmask) > kprefix, or equal with (id & imask) <= iprefix
+    uint32_t kprefix = 0, kmask = 0, need = (uint32_t)k;
+    uint64_t iprefix = 0, imask = 0;
+    for (int pass = 0; pass < 4 + id_passes; ++pass) {
+        const bool on_key = pass < 4;
+        const int shift = on_key ? 24 - 8 * pass : 8 * (id_passes - 1 - (pass - 4));
+        hist[tid] = 0;
+        __syncthreads();
+        visit([&](uint32_t key, int64_t id) {
+            if ((key & kmask) != kprefix || ((uint64_t)id & imask) != iprefix) return;
+            const uint32_t d = on_key ? (key >> shift) & 255u : 255u - (uint32_t)(((uint64_t)id >> shift) & 255u);
+            atomicAdd(&hist[d], 1u);
+        });
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t acc = 0;
+            int d = 255;
+            for (; d >= 0; --d) {
+                if (acc + hist[d] >= need) break;
+                acc += hist[d];
+            }
+            // d < 0: fewer than `need` candidates in all (only on pass 0): every one is taken
+            sh_state = d < 0 ? 2u : (acc + hist[d] == need ? 1u : 0u);
+            sh_digit = (uint32_t)(d < 0 ? 0 : d);
+            sh_need = need - acc;
+        }
+        __syncthreads();
+        const uint32_t state = sh_state, d = sh_digit;
+        need = sh_need;
+        if (state == 2u) break;                            // masks still zero: the rule above takes everything
+        if (on_key) { kprefix |= d << shift; kmask |= 255u << shift; }
+        else { iprefix |= (uint64_t)(255u - d) << shift; imask |= (uint64_t)255u << shift; }
+        if (state == 1u) break;                            // the bin is taken whole: nothing left to decide
+    }
+
+    const int kp = k <= 1 ? 1 : 1 << (32 - __builtin_clz((unsigned)(k - 1)));     // next power of two
+    if (tid == 0) sh_cnt = 0;
+    for (int i = tid; i < kp; i += 256) { sk[i] = 0u; si[i] = INT64_MAX; }
+    __syncthreads();
+    visit([&](uint32_t key, int64_t id) {
+        const uint32_t hi = key & kmask;
+        if (hi > kprefix || (hi == kprefix && ((uint64_t)id & imask) <= iprefix)) {
+            const uint32_t pos = atomicAdd(&sh_cnt, 1u);
+            if (pos < (uint32_t)k) { sk[pos] = key; si[pos] = id; }     // more than k only if an id came in twice
+        }
+    });
+    __syncthreads();
+    // bitonic sort of kp entries: descending key, ascending id among equal keys; empty slots (id INT64_MAX) go last
+    for (int size = 2; size <= kp; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (kp >> 1); t += 256) {
+                const int lo = 2 * t - (t & (stride - 1));
+                const int hi = lo + stride;
+                const bool desc = ((lo & size) == 0);
+                const uint32_t a = sk[lo], b = sk[hi];
+                const int64_t ia = si[lo], ib = si[hi];
+                const bool ea = ia == INT64_MAX, eb = ib == INT64_MAX;
+                const bool a_first = ea != eb ? eb : (a > b) || (a == b && ia < ib);       // a ranks before b
+                if (desc ? !a_first : a_first) { sk[lo] = b; sk[hi] = a; si[lo] = ib; si[hi] = ia; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < k; i += 256) {
+        const bool empty = si[i] == INT64_MAX;
+        rs[i] = empty ? -INFINITY : fkey_inv(sk[i]);
+        rx[i] = empty ? -1 : si[i];
+    }
+}
+
 // Euclidean score 1 / (1 + ||q - c||_2): the reference's own third score function (models/evaluators.py:392-405,
 // `1 / (1 + torch.cdist(a, b, p=2))`, passed as score_functions['euclid_score'] by training/main.py:57 and
 // ir_evauation_script.py:71). Distances are summed from the differences themselves (an fp32 FMA chain per pair): the
@@ -238,13 +371,18 @@ static int score_block(const float* qn, const float* cn, int rows, int nc, int n
     return qst_gemm_nt_x3(&g, 0, st);
 }
 
+// a null side is left alone (the streaming path prepares the queries once and then one corpus chunk at a time)
 static int prep_operands(const float* queries, const float* corpus, int nq, int nc, int dim, int mode, float* qn, float* cn,
                          hipStream_t st) {
     const int nqp = (int)pad4(nq), ncp = (int)pad4(nc);
-    prep_rows_kernel<<<(nqp + 3) / 4, 256, 0, st>>>(queries, nq, nqp, dim, mode == QST_SCORE_COS, qn);
-    QST_LAUNCH_CHECK();
-    prep_rows_kernel<<<(ncp + 3) / 4, 256, 0, st>>>(corpus, nc, ncp, dim, mode == QST_SCORE_COS, cn);
-    QST_LAUNCH_CHECK();
+    if (queries) {
+        prep_rows_kernel<<<(nqp + 3) / 4, 256, 0, st>>>(queries, nq, nqp, dim, mode == QST_SCORE_COS, qn);
+        QST_LAUNCH_CHECK();
+    }
+    if (corpus) {
+        prep_rows_kernel<<<(ncp + 3) / 4, 256, 0, st>>>(corpus, nc, ncp, dim, mode == QST_SCORE_COS, cn);
+        QST_LAUNCH_CHECK();
+    }
     return QST_OK;
 }
 
@@ -270,6 +408,62 @@ static int topk_scores_impl(const float* queries, const float* corpus, int nq, i
         topk_rows_kernel<<<rows, 256, 0, st>>>(sc, ncp, nullptr, nc, k, cap, out_scores + (size_t)q0 * k,
                                                out_index + (size_t)q0 * k);
         QST_LAUNCH_CHECK();
+    }
+    return QST_OK;
+}
+
+extern "C" int qst_topk_merge_rows(const float* scores, int64_t ld, int nrows, int n, int64_t col_base, int64_t row_base,
+                                   int exclude_self, float max_score, int k, float* run_scores, int64_t* run_index,
+                                   void* stream) {
+    if (!scores || !run_scores || !run_index || nrows <= 0 || n <= 0 || k <= 0 || ld < n) return QST_ERR_BAD_ARG;
+    if (col_base < 0 || row_base < 0 || col_base > INT64_MAX - n || row_base > INT64_MAX - nrows) return QST_ERR_BAD_ARG;
+    if (max_score != max_score) return QST_ERR_BAD_ARG;
+    if (k > TOPK_MAX) return QST_ERR_UNSUPPORTED;
+    topk_merge_kernel<<<nrows, 256, 0, (hipStream_t)stream>>>(scores, ld, n, col_base, row_base, exclude_self, max_score, k,
+                                                              run_scores, run_index);
+    QST_LAUNCH_CHECK();
+    return QST_OK;
+}
+
+extern "C" size_t qst_topk_stream_workspace_bytes(int nq, int chunk, int dim) {
+    return qst_topk_workspace_bytes(nq, chunk, dim);        // the same three parts, with one chunk in the corpus's place
+}
+
+extern "C" int qst_topk_stream(const float* queries, const float* corpus, int nq, int nc, int dim, int k, int mode, int chunk,
+                               int64_t query_base, int64_t corpus_base, int exclude_self, float max_score,
+                               float* run_scores, int64_t* run_index, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    if (!queries || !corpus || !run_scores || !run_index || !workspace || nq <= 0 || nc <= 0 || dim <= 0 || k <= 0 ||
+        chunk <= 0)
+        return QST_ERR_BAD_ARG;
+    if (mode != QST_SCORE_DOT && mode != QST_SCORE_COS && mode != QST_SCORE_EUCLID) return QST_ERR_BAD_ARG;
+    if (query_base < 0 || corpus_base < 0 || query_base > INT64_MAX - nq || corpus_base > INT64_MAX - nc)
+        return QST_ERR_BAD_ARG;
+    if (max_score != max_score) return QST_ERR_BAD_ARG;
+    if (k > TOPK_MAX || dim % 32 != 0) return QST_ERR_UNSUPPORTED;
+    if (chunk > nc) chunk = nc;
+    if (workspace_bytes < qst_topk_stream_workspace_bytes(nq, chunk, dim)) return QST_ERR_WORKSPACE;
+    if ((int64_t)pad4(chunk) * dim * 4 >= 0x7FFFFF00LL) return QST_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const int nqp = (int)pad4(nq);
+    float* qn = (float*)workspace;
+    float* cn = qn + (size_t)nqp * dim;
+    float* sc = cn + pad4(chunk) * dim;
+    int rc = prep_operands(queries, nullptr, nq, 0, dim, mode, qn, nullptr, st);
+    if (rc != QST_OK) return rc;
+    for (int c0 = 0; c0 < nc; c0 += chunk) {
+        const int cols = nc - c0 < chunk ? nc - c0 : chunk;
+        const int colsp = (int)pad4(cols);
+        rc = prep_operands(nullptr, corpus + (size_t)c0 * dim, 0, cols, dim, mode, nullptr, cn, st);
+        if (rc != QST_OK) return rc;
+        for (int q0 = 0; q0 < nq; q0 += kQueryBlock) {
+            const int rows = nq - q0 < kQueryBlock ? nq - q0 : kQueryBlock;
+            rc = score_block(qn + (size_t)q0 * dim, cn, rows, cols, colsp, dim, mode, sc, st);
+            if (rc != QST_OK) return rc;
+            topk_merge_kernel<<<rows, 256, 0, st>>>(sc, colsp, cols, corpus_base + c0, query_base + q0, exclude_self,
+                                                    max_score, k, run_scores + (size_t)q0 * k, run_index + (size_t)q0 * k);
+            QST_LAUNCH_CHECK();
+        }
     }
     return QST_OK;
 }

@@ -1,7 +1,8 @@
 """sentence_transformers.evaluation surface used by the reference's evaluators (models/evaluators.py:9-12,187-216,
 572-612; ir_evauation_script.py:107-131): the base class, SimilarityFunction, SequentialEvaluator, an encode()-driven
 TripletEvaluator and InformationRetrievalEvaluator, whose scoring + top-k run on the GPU
-through libqst (util.topk_scores), and EmbeddingSimilarityEvaluator (graded pairs; qst_pair_metric). The two evaluators the
+through libqst (util.topk_scores), EmbeddingSimilarityEvaluator (graded pairs; qst_pair_metric) and
+ParaphraseMiningEvaluator (util.paraphrase_mining on the streaming top-k, qst_topk_stream). The two evaluators the
 reference selects its models with, QuadrupletEvaluator (qst_quadruplet_eval) and QuadrupletLossEvaluator, and the chain
 get_sequential_evaluator builds of them stand at the end."""
 from __future__ import annotations
@@ -392,6 +393,110 @@ def _append_csv(path: str, headers: List[str], row: list) -> None:
         if new:
             w.writerow(headers)
         w.writerow(row)
+
+
+def paraphrase_metrics(pairs, ids, duplicates) -> Dict[str, float]:
+    """The metrics of a mined pair list, host arithmetic only. pairs: [score, i, j] best first (util.paraphrase_mining),
+    ids[i] the id of row i, duplicates: the set of gold pairs as frozensets of two ids. Walking the list, after the n-th
+    pair precision = correct / n, recall = correct / len(duplicates), f1 their harmonic mean (0 where both are 0).
+    average_precision sums the precision at the positions that are duplicates and divides by len(duplicates). The best
+    f1 (the first, where several positions share it) keeps its precision and recall; its threshold is the mean of that
+    pair's score and the next pair's, or the pair's own score at the end of the list. All zero for an empty list or no
+    gold pairs."""
+    out = {"precision": 0.0, "recall": 0.0, "f1": 0.0, "threshold": 0.0, "average_precision": 0.0}
+    total = len(duplicates)
+    if total == 0:
+        return out
+    correct, ap = 0, 0.0
+    for n, (score, i, j) in enumerate(pairs, start=1):
+        hit = frozenset((ids[i], ids[j])) in duplicates
+        correct += int(hit)
+        precision, recall = correct / n, correct / total
+        f1 = 2 * correct / (n + total)          # = 2 P R / (P + R), in the form that gives equal cuts equal floats
+        if hit:
+            ap += precision
+        if f1 > out["f1"]:
+            nxt = pairs[n][0] if n < len(pairs) else score
+            out.update(precision=precision, recall=recall, f1=f1, threshold=(score + nxt) / 2)
+    out["average_precision"] = ap / total
+    return out
+
+
+def duplicate_closure(pairs) -> Set[frozenset]:
+    """Every two members of a connected component of the duplicate graph count as duplicates: the gold pairs with their
+    transitive closure, as frozensets of two ids."""
+    parent = {}
+
+    def find(x):
+        while parent.setdefault(x, x) != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for p in pairs:
+        a, b = tuple(p)
+        parent[find(a)] = find(b)
+    groups = {}
+    for x in list(parent):
+        groups.setdefault(find(x), []).append(x)
+    return {frozenset((g[a], g[b])) for g in groups.values() for a in range(len(g)) for b in range(a + 1, len(g))}
+
+
+class ParaphraseMiningEvaluator(SentenceEvaluator):
+    """sentence-transformers 2.2.2's ParaphraseMiningEvaluator: mine the most similar sentence pairs of `sentences_map`
+    ({id: sentence}) with util.paraphrase_mining -- encode once, then for every sentence its top_k best others by the
+    streaming top-k on the device -- and score the ranked pair list against the gold duplicates: precision, recall and
+    F1 at the best-F1 cut, the score threshold of that cut, and the average precision, which is returned.
+
+    Duplicates are unordered id pairs, given as duplicates_list [(id1, id2)] and / or duplicates_dict {id1: {id2: bool}};
+    pairs that name an id outside sentences_map, or one id twice, are dropped. With add_transitive_closure every two
+    members of a connected component count. The mined list does not depend on the chunk sizes (util.paraphrase_mining_
+    embeddings says where that differs from ST)."""
+
+    def __init__(self, sentences_map: Dict[str, str], duplicates_list=None, duplicates_dict=None,
+                 add_transitive_closure: bool = False, query_chunk_size: int = 5000, corpus_chunk_size: int = 100000,
+                 max_pairs: int = 500000, top_k: int = 100, show_progress_bar: bool = False, batch_size: int = 16,
+                 name: str = "", write_csv: bool = True):
+        if not sentences_map:
+            raise ValueError("sentences_map is empty")
+        if duplicates_list is None and duplicates_dict is None:
+            raise ValueError("give the gold duplicates as duplicates_list and / or duplicates_dict")
+        if not 1 <= top_k <= 1024:
+            raise ValueError(f"top_k must be between 1 and 1024 (got {top_k})")
+        if max_pairs < 1 or query_chunk_size < 1 or corpus_chunk_size < 1 or batch_size < 1:
+            raise ValueError("max_pairs, query_chunk_size, corpus_chunk_size and batch_size must be positive")
+        self.ids = list(sentences_map.keys())
+        self.sentences = [sentences_map[i] for i in self.ids]
+        gold = set()
+        for a, b in (duplicates_list or []):
+            gold.add(frozenset((a, b)))
+        for a, others in (duplicates_dict or {}).items():
+            for b, flag in others.items():
+                if flag:
+                    gold.add(frozenset((a, b)))
+        gold = {p for p in gold if len(p) == 2 and all(x in sentences_map for x in p)}
+        self.duplicates = duplicate_closure(gold) if add_transitive_closure else gold
+        self.total_num_duplicates = len(self.duplicates)
+        self.query_chunk_size, self.corpus_chunk_size = query_chunk_size, corpus_chunk_size
+        self.max_pairs, self.top_k = max_pairs, top_k
+        self.show_progress_bar, self.batch_size, self.name, self.write_csv = show_progress_bar, batch_size, name, write_csv
+        self.csv_file = "paraphrase_mining_evaluation" + ("_" + name if name else "") + "_results.csv"
+        self.csv_headers = ["epoch", "steps", "precision", "recall", "f1", "threshold", "average_precision"]
+
+    def mine(self, model):
+        from . import util
+        return util.paraphrase_mining(model, self.sentences, self.show_progress_bar, self.batch_size,
+                                      self.query_chunk_size, self.corpus_chunk_size, self.max_pairs, self.top_k)
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1) -> float:
+        m = paraphrase_metrics(self.mine(model), self.ids, self.duplicates)
+        LOGGER.info("ParaphraseMiningEvaluator %s: epoch %d, steps %d: AP %.4f, best F1 %.4f (precision %.4f, recall %.4f) "
+                    "at threshold %.4f", self.name, epoch, steps, m["average_precision"], m["f1"], m["precision"],
+                    m["recall"], m["threshold"])
+        if output_path is not None and self.write_csv:
+            _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers,
+                        [epoch, steps, m["precision"], m["recall"], m["f1"], m["threshold"], m["average_precision"]])
+        return m["average_precision"]
 
 
 def _unwrap_example(example):

@@ -1,7 +1,9 @@
 """sentence_transformers.util functions the reference imports (training/main.py:6, models/evaluators.py:9-12):
 cos_sim, dot_score, batch_to_device -- plus euclidean_score, the reference's own third score function
 (models/evaluators.py:392-405). All three score matrices come from libqst (qst_score_matrix: row normalisation, the
-split-bf16 x3 GEMM or the direct-difference Euclidean kernel); there is no torch arithmetic and no CPU path here."""
+split-bf16 x3 GEMM or the direct-difference Euclidean kernel); there is no torch arithmetic and no CPU path here.
+semantic_search, paraphrase_mining and paraphrase_mining_embeddings (ST 2.2.2 signatures) stand on the streaming top-k
+(qst_topk_stream / qst_topk_merge_rows); of them only merge_mined_pairs, the pair bookkeeping, is host numpy."""
 from __future__ import annotations
 
 import numpy as np
@@ -129,6 +131,185 @@ def topk_rows(scores: torch.Tensor, k: int, index_map: torch.Tensor = None):
     _lib.check(lib.qst_topk_rows(s.data_ptr(), n, _lib.ptr(im), n_rows, n, k, out_s.data_ptr(), out_i.data_ptr(),
                                  _lib.current_stream_ptr()), "qst_topk_rows")
     return out_s, out_i
+
+
+# corpus rows per chunk of the streaming top-k where the caller does not say: the score block is
+# [min(nq, 2048), chunk] fp32, 128 MB at most here. The result does not depend on it; of 16,384 / 65,536 / 262,144 it
+# was the fastest at 2048 x 262,144 x 384 for k = 10 and k = 100 (profiles/topk_stream_bench.json).
+STREAM_CHUNK = 16384
+TOPK_MAX = 1024
+
+
+def _new_state(nq: int, k: int, device):
+    return (torch.full((nq, k), float("-inf"), dtype=torch.float32, device=device),
+            torch.full((nq, k), -1, dtype=torch.int64, device=device))
+
+
+def _check_state(state, nq: int, k: int, device):
+    s, i = state
+    if not (torch.is_tensor(s) and torch.is_tensor(i) and s.dtype == torch.float32 and i.dtype == torch.int64
+            and tuple(s.shape) == (nq, k) and tuple(i.shape) == (nq, k) and s.device == device and i.device == device
+            and s.is_contiguous() and i.is_contiguous()):
+        raise ValueError(f"state must be the (scores f32, indices int64) pair of shape {(nq, k)} an earlier call returned")
+    return s, i
+
+
+def topk_merge_rows(scores: torch.Tensor, k: int, col_base: int = 0, row_base: int = 0, exclude_self: bool = False,
+                    max_score: float = float("inf"), state=None):
+    """Merge one chunk of a score matrix into a running top-k (libqst qst_topk_merge_rows): column j of `scores` is
+    global id col_base + j, row r is query row_base + r. Returns (scores [rows, k], indices int64 [rows, k]) sorted by
+    (score descending, id ascending), padded with -inf / -1; pass the pair back as `state` with the next chunk (it is
+    updated in place)."""
+    from . import _lib
+    lib = _lib.load()
+    if not scores.is_cuda:
+        raise _lib.QstError("topk_merge_rows runs on the HIP device: pass a CUDA tensor (there is no CPU fallback)")
+    s = scores.to(torch.float32).contiguous()
+    rows, n = s.shape
+    rs, ri = _new_state(rows, k, s.device) if state is None else _check_state(state, rows, k, s.device)
+    with torch.cuda.device(s.device):
+        _lib.check(lib.qst_topk_merge_rows(s.data_ptr(), n, rows, n, int(col_base), int(row_base), int(bool(exclude_self)),
+                                           float(max_score), k, rs.data_ptr(), ri.data_ptr(), _lib.current_stream_ptr()),
+                   "qst_topk_merge_rows")
+    return rs, ri
+
+
+def topk_stream(queries, corpus, k: int, mode="cos", chunk: int = STREAM_CHUNK, exclude_self: bool = False,
+                max_score: float = float("inf"), state=None, query_base: int = 0, corpus_base: int = 0):
+    """The k best corpus rows for every query row at any corpus size (libqst qst_topk_stream): the corpus goes through
+    in chunks of `chunk` rows -- prepare, score, merge into a running top-k -- so the workspace is bounded by the chunk
+    and the result, ties included, is the same for every chunk size. mode: 'dot' | 'cos' | 'euclid'. Query row r has
+    global id query_base + r, corpus row c has corpus_base + c; exclude_self drops the corpus row whose id is the
+    query's own, max_score those scoring above it. Returns (scores [nq, k] descending, indices int64 [nq, k]), padded
+    with -inf / -1 where fewer than k rows qualify. Passing the pair back as `state`, with the next piece of the corpus
+    and its corpus_base, continues the search (the pair is updated in place). No CPU fallback."""
+    from . import _lib
+    lib = _lib.load()
+    m = _mode(mode)
+    q = _device_rows(queries)
+    c = _device_rows(corpus, q.device)
+    if c.device != q.device:
+        c = c.to(q.device)
+    if q.shape[1] != c.shape[1]:
+        raise ValueError(f"embedding sizes differ: {tuple(q.shape)} vs {tuple(c.shape)}")
+    nq, dim = q.shape
+    nc = c.shape[0]
+    chunk = max(1, min(int(chunk), nc))
+    rs, ri = _new_state(nq, k, q.device) if state is None else _check_state(state, nq, k, q.device)
+    with torch.cuda.device(q.device):
+        ws = torch.empty(lib.qst_topk_stream_workspace_bytes(nq, chunk, dim), dtype=torch.uint8, device=q.device)
+        _lib.check(lib.qst_topk_stream(q.data_ptr(), c.data_ptr(), nq, nc, dim, k, m, chunk, int(query_base),
+                                       int(corpus_base), int(bool(exclude_self)), float(max_score), rs.data_ptr(),
+                                       ri.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+                   "qst_topk_stream")
+    return rs, ri
+
+
+def _as_rows(x):
+    """A tensor, a numpy array, a list of tensors or a single 1-D embedding -> a 2-D tensor (ST's accepted inputs)."""
+    if isinstance(x, (list, tuple)):
+        x = torch.stack([torch.as_tensor(t) for t in x])
+    return _as_2d(x)
+
+
+def _search(queries, corpus, top_k: int, score_function, query_chunk_size: int, corpus_chunk_size: int,
+            exclude_self: bool):
+    """(scores [nq, k], corpus rows int64 [nq, k]) on the device, k = min(top_k, TOPK_MAX checked), over the WHOLE
+    corpus. The package's own score functions run qst_topk_stream; any other callable is applied per
+    (query chunk, corpus chunk) and its matrix goes through qst_topk_merge_rows."""
+    if not 1 <= int(top_k) <= TOPK_MAX:
+        raise ValueError(f"top_k must be between 1 and {TOPK_MAX} (got {top_k})")
+    if query_chunk_size < 1 or corpus_chunk_size < 1:
+        raise ValueError("query_chunk_size and corpus_chunk_size must be positive")
+    if not callable(score_function):
+        raise ValueError(f"score_function must be callable (got {type(score_function).__name__})")
+    top_k = int(top_k)
+    mode = getattr(score_function, "_qst_mode", None)
+    if mode is not None:
+        # the library blocks the queries itself; the chunk sizes only bound memory and do not change the result
+        return topk_stream(queries, corpus, top_k, mode=int(mode), chunk=min(int(corpus_chunk_size), STREAM_CHUNK),
+                           exclude_self=exclude_self)
+    from . import _lib
+    q = _as_2d(queries)
+    if not q.is_cuda:
+        if not torch.cuda.is_available():
+            raise _lib.QstError("the search runs on the HIP device and none is visible (there is no CPU path)")
+        q = q.to(torch.device("cuda", torch.cuda.current_device()))
+    c = _as_2d(corpus).to(q.device)
+    rs, ri = _new_state(q.shape[0], top_k, q.device)
+    for q0 in range(0, q.shape[0], query_chunk_size):
+        q1 = min(q0 + query_chunk_size, q.shape[0])
+        state = (rs[q0:q1], ri[q0:q1])                       # row slices of contiguous tensors: contiguous views
+        for c0 in range(0, c.shape[0], corpus_chunk_size):
+            c1 = min(c0 + corpus_chunk_size, c.shape[0])
+            full = torch.as_tensor(score_function(q[q0:q1], c[c0:c1])).to(q.device, torch.float32)
+            if tuple(full.shape) != (q1 - q0, c1 - c0):
+                raise ValueError(f"score_function returned shape {tuple(full.shape)}, expected {(q1 - q0, c1 - c0)}")
+            topk_merge_rows(full, top_k, col_base=c0, row_base=q0, exclude_self=exclude_self, state=state)
+    return rs, ri
+
+
+def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int = 100, corpus_chunk_size: int = 500000,
+                    top_k: int = 10, score_function=cos_sim):
+    """sentence_transformers.util.semantic_search (2.2.2): for every query the top_k corpus entries, one list per query
+    of {'corpus_id': int, 'score': float} in descending order (ties: ascending corpus_id); shorter than top_k where the
+    corpus is. Inputs: a tensor, a numpy array, a list of tensors, or 1-D for a single one; they are moved to the HIP
+    device (there is no CPU path). cos_sim, dot_score and euclidean_score of this package run the streaming top-k
+    (qst_topk_stream: scoring and selection in one call, no [nq, nc] matrix); any other callable is applied per
+    (query chunk, corpus chunk) and selected by qst_topk_merge_rows. The chunk sizes bound memory only."""
+    rs, ri = _search(_as_rows(query_embeddings), _as_rows(corpus_embeddings), top_k, score_function, query_chunk_size,
+                     corpus_chunk_size, exclude_self=False)
+    sc, idx = rs.cpu().numpy(), ri.cpu().numpy()
+    return [[{"corpus_id": int(c), "score": float(s)} for s, c in zip(sc[r], idx[r]) if c >= 0] for r in range(len(sc))]
+
+
+def merge_mined_pairs(scores, rows, cols, max_pairs: int):
+    """The host half of paraphrase mining, pure numpy: candidates (score, i, j) -- row i found row j -- become the
+    list of unordered pairs [score, min(i, j), max(i, j)]. The max_pairs best candidates by (score descending, min
+    ascending, max ascending) are kept FIRST; then the two directions of a pair merge into one entry with the larger
+    score; the list comes back in the same order. Entries with j < 0 (empty top-k slots) or i == j are dropped."""
+    s = np.asarray(scores, dtype=np.float64).ravel()
+    i = np.asarray(rows, dtype=np.int64).ravel()
+    j = np.asarray(cols, dtype=np.int64).ravel()
+    if not (len(s) == len(i) == len(j)):
+        raise ValueError("scores, rows and cols must have the same length")
+    if max_pairs < 1:
+        raise ValueError(f"max_pairs must be positive (got {max_pairs})")
+    keep = (j >= 0) & (i >= 0) & (i != j)
+    s, lo, hi = s[keep], np.minimum(i, j)[keep], np.maximum(i, j)[keep]
+    order = np.lexsort((hi, lo, -s))[:max_pairs]
+    s, lo, hi = s[order], lo[order], hi[order]
+    # the first occurrence of a pair in this order carries its larger score
+    _, first = np.unique(np.stack([lo, hi], axis=1), axis=0, return_index=True) if len(s) else (None, np.zeros(0, np.int64))
+    first = np.sort(first)
+    return [[float(s[t]), int(lo[t]), int(hi[t])] for t in first]
+
+
+def paraphrase_mining_embeddings(embeddings, query_chunk_size: int = 5000, corpus_chunk_size: int = 100000,
+                                 max_pairs: int = 500000, top_k: int = 100, score_function=cos_sim):
+    """sentence_transformers.util.paraphrase_mining_embeddings (2.2.2): the most similar pairs among the rows of
+    `embeddings`, as a list of [score, i, j] with i < j, each pair once, sorted by (score descending, i, j).
+
+    Device: for every row its top_k best OTHER rows (the streaming top-k with exclude_self; score_function as in
+    semantic_search). Host: merge_mined_pairs keeps the max_pairs best candidates and merges the two directions.
+
+    One deliberate difference from ST 2.2.2: ST takes top_k (+1 for the row itself) per corpus chunk, so its candidate
+    set, and with it the answer, depends on corpus_chunk_size. Here the top_k are selected over the whole corpus and
+    the chunk sizes bound memory only. The two agree whenever the corpus fits one chunk and the scores have no ties."""
+    e = _as_rows(embeddings)
+    rs, ri = _search(e, e, top_k, score_function, query_chunk_size, corpus_chunk_size, exclude_self=True)
+    sc, idx = rs.cpu().numpy(), ri.cpu().numpy()
+    rows = np.broadcast_to(np.arange(sc.shape[0], dtype=np.int64)[:, None], sc.shape)
+    return merge_mined_pairs(sc, rows, idx, max_pairs)
+
+
+def paraphrase_mining(model, sentences, show_progress_bar: bool = False, batch_size: int = 32,
+                      query_chunk_size: int = 5000, corpus_chunk_size: int = 100000, max_pairs: int = 500000,
+                      top_k: int = 100, score_function=cos_sim):
+    """sentence_transformers.util.paraphrase_mining (2.2.2): encode the sentences with `model`, then
+    paraphrase_mining_embeddings. Returns [score, i, j] with i < j indexing `sentences`."""
+    emb = model.encode(list(sentences), show_progress_bar=show_progress_bar, batch_size=batch_size, convert_to_tensor=True)
+    return paraphrase_mining_embeddings(emb, query_chunk_size, corpus_chunk_size, max_pairs, top_k, score_function)
 
 
 def mine_hard_negatives(references, candidates, k: int, threshold: float = 0.2, embedder=None, batch_size: int = 64):
