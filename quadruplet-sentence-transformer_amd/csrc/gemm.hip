@@ -975,9 +975,15 @@ __device__ __forceinline__ uint32_t tn_off(int row, int chunk) {
 __device__ __forceinline__ op16x4 lds_tr16(const char* p) {
     return lds_tr16_op(p);
 }
+// ... at an LDS byte address (the stage loop of the grouped wgrad keeps its addresses as integers: base + immediate offset)
+__device__ __forceinline__ op16x4 lds_tr16_at(uint32_t a) {
+    typedef __attribute__((ext_vector_type(4))) __bf16 raw4;
+    return __builtin_bit_cast(op16x4, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) raw4*)(uintptr_t)a));
+}
 
-// Wave roles: waves 0-3 run the MFMAs (one per SIMD, the whole register file to themselves), waves 4-7 are loaders
-// that issue every LDS-DMA (waves 4,5: the two halves of the dY stage, waves 6,7: of the X stage). In-kernel stamps on the earlier
+// Wave roles: waves 0-3 run the MFMAs (one per SIMD), waves 4-7 are loaders that issue every LDS-DMA (waves 4,5: the two
+// halves of the dY stage, waves 6,7: of the X stage). Registers are allocated per kernel, not per role: each SIMD holds one
+// MFMA wave and one loader wave of 256 VGPRs each, and the loader keeps a dozen live. In-kernel stamps on the earlier
 // all-waves-load version showed 2800 cycles per 32-row stage for 672 cycles of MFMA: an in-order wave pays the DMA
 // issue cost (60-185 cycles per instruction) and the LDS read latency in series with its MFMAs; with loaders it is 990.
 //
@@ -1051,10 +1057,16 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
             constexpr int NDMA = TBK * 24 / 64 / 2;       // DMA instructions per loader wave and stage (1 KB each): 12
             uint32_t vo[NDMA];
 #pragma unroll
-            for (int t = 0; t < NDMA; ++t) {
-                const int pp = (half * NDMA + t) * 64 + lane;
+            for (int b = 0; b < 3; ++b) {
+                // three DMAs are 192 positions = 8 whole rows: DMA t + 3 has the chunk (and the swizzle: row bit 1) of DMA t,
+                // 8 rows further down -- three lane values to keep across tasks instead of twelve (kept as twelve, the
+                // kernel spilled 22 VGPRs and every task began with eight dependent scratch reloads in the loaders)
+                const int pp = (half * NDMA + b) * 64 + lane;
                 const int row = pp / 24, chunk = (pp % 24) ^ tn_swz(row);
-                vo[t] = (c0 + chunk * 8 < width) ? (uint32_t)row * ld * 2u + chunk * 16u : kOOB;
+                const bool ok = c0 + chunk * 8 < width;
+#pragma unroll
+                for (int t = b; t < NDMA; t += 3)
+                    vo[t] = ok ? (uint32_t)(row + 8 * (t / 3)) * ld * 2u + chunk * 16u : kOOB;
             }
             auto issue = [&](int mt) {
                 char* st = smem + (mt % TSTAGES) * TT_STAGE + (isA ? 0 : TT_TILE);
@@ -1064,8 +1076,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
             };
             // All TSTAGES-1 slots that are not being read are kept in flight (120 KB per CU). Timing experiments on this
             // kernel (same-process A/B): MFMAs compiled out -17%, atomic flush compiled out -16%, constant LDS slot
-            // (no per-stage address arithmetic) -8%, two -> four loaders and 72 -> 120 KB in flight -1.7% together:
-            // no single resource bounds it; the skeleton of barriers + L2->LDS streaming is 70% of the time.
+            // (no per-stage address arithmetic; round 6 took most of it: la / lb below) -8%, two -> four loaders and
+            // 72 -> 120 KB in flight -1.7% together: no single resource bounds it; the skeleton of barriers + L2->LDS
+            // streaming is 70% of the time.
             constexpr int AHEAD = TSTAGES - 1;
 #pragma unroll 1
             for (int st = 0; st < AHEAD && st < nm; ++st) issue(st);
@@ -1091,11 +1104,29 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
         const bool do_bias = (g.colsum != nullptr) && (k0 == 0) && (wn == 0);
+        // Fragment-read addresses: read (ks, i, jj) of a stage is at slot + la[i] + (ks * 16 + 4 * jj) * 384 -- the swizzle of
+        // its row is the lane's alone (row bit 1 = q bit 1: ks * 16, 8 * fh and 4 * jj leave it), so three lane offsets per
+        // operand and an immediate cover the 48 reads of a stage: six adds per stage instead of one or two per read.
+        uint32_t la[3], lb[3];
+        {
+            const uint32_t lr = (uint32_t)(8 * fh + q) * 384u + 8u * (p & 1), g2 = gsel * 2 + (p >> 1);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                la[i] = lr + (uint32_t)(((wm * 12 + i * 4 + g2) ^ tn_swz(q)) << 4);
+                lb[i] = lr + TT_TILE + (uint32_t)(((wn * 12 + i * 4 + g2) ^ tn_swz(q)) << 4);
+            }
+        }
+        uint32_t slot = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;      // of stage mt: mt % TSTAGES
 
         for (int mt = 0; mt < nm; ++mt) {
             __builtin_amdgcn_s_barrier();                  // stage mt landed (the loaders waited for it before arriving)
-            const char* pa = smem + (mt % TSTAGES) * TT_STAGE;
-            const char* pb = pa + TT_TILE;
+            uint32_t ra[3], rb[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                ra[i] = slot + la[i]; rb[i] = slot + lb[i];
+                asm volatile("" : "+v"(ra[i]), "+v"(rb[i]));      // kept as they are: the reads fold the rest into their offset field
+            }
+            slot = (mt % TSTAGES == TSTAGES - 1) ? slot - (TSTAGES - 1) * TT_STAGE : slot + TT_STAGE;
             // One MFMA wave per SIMD: nothing but its own instruction stream hides the LDS latency of its fragment reads. The
             // fragments of k-step ks + 1 are therefore read into a second register set while the MFMAs of ks issue (hipcc's own
             // schedule reads a k-step's 12 fragments, waits, multiplies: ~250 exposed cycles per 288 of MFMA, in-kernel stamps
@@ -1105,11 +1136,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
     do {                                                                                                    \
         _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                                     \
             _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                                              \
-                const int row = (ks_) * 16 + 8 * fh + 4 * jj + q;                                           \
-                const int ca = wm * 12 + i * 4 + gsel * 2 + (p >> 1);                                       \
-                const int cb = wn * 12 + i * 4 + gsel * 2 + (p >> 1);                                       \
-                const op16x4 ta = lds_tr16(pa + tn_off(row, ca) + 8 * (p & 1));                             \
-                const op16x4 tb = lds_tr16(pb + tn_off(row, cb) + 8 * (p & 1));                             \
+                const op16x4 ta = lds_tr16_at(ra[i] + ((ks_) * 16 + 4 * jj) * 384);                         \
+                const op16x4 tb = lds_tr16_at(rb[i] + ((ks_) * 16 + 4 * jj) * 384);                         \
                 _Pragma("unroll") for (int e = 0; e < 4; ++e) { fa[set_][i][jj * 4 + e] = ta[e]; fb[set_][i][jj * 4 + e] = tb[e]; } \
             }                                                                                               \
         }                                                                                                   \
