@@ -283,6 +283,30 @@ int qst_quadruplet_eval(const float* xa, const float* xp, const float* xq, const
                         float* out_dist, int32_t* out_flags, int32_t* out_counts, void* stream);
 
 /*
+ * MultipleNegativesRankingLoss and MultipleNegativesSymmetricRankingLoss of sentence-transformers 2.2.2 (version 105;
+ * csrc/mnrl.hip): in-batch negatives. a fp32 [B, D] anchors, c fp32 [N, D] candidates, N >= B, rows contiguous; candidate i
+ * (i < B) is the positive of anchor i, rows B .. N-1 are further negatives (the text columns after the second, stacked).
+ *   S = scale * sim(a, c) [B, N], sim = QST_SCORE_COS (util.cos_sim: both sides through F.normalize(p=2, dim=1, eps=1e-12))
+ *       or QST_SCORE_DOT (util.dot_score); QST_SCORE_EUCLID is refused
+ *   symmetric = 0: out_loss[0] = mean_i(logsumexp_j S[i, j] - S[i, i])             = F.cross_entropy(S, arange(B))
+ *   symmetric = 1: (that + F.cross_entropy(S[:, :B].T, arange(B))) / 2
+ * grad_a [B, D] and grad_c [N, D] both NULL = forward only (nothing else is written); exactly one NULL is
+ * QST_ERR_BAD_ARG. For cos the gradients pass through the normalisation as torch's autograd does: a row with |x| < 1e-12
+ * has the normalised row 0 and the gradient d_hat / 1e-12. grad_out: fp32 [1] on the DEVICE (NULL = 1), read by the
+ * kernels -- no host synchronisation, capturable in a HIP graph; it multiplies the finished gradients, so a call with
+ * grad_out = g returns the correctly rounded g * (the gradients without).
+ * B < 1, N < B, D < 1, a NULL input, out_loss or workspace, a workspace smaller than qst_mnrl_workspace_bytes(B, N, D) or not
+ * 4-byte aligned, a scale that is not finite and positive, another sim or symmetric: QST_ERR_BAD_ARG before any launch,
+ * nothing written. B * ldS (ldS = N rounded up to 4) or N * D past 2^31 - 1: QST_ERR_UNSUPPORTED. Any other B, N, D is
+ * accepted (16-byte accesses when D % 4 == 0 and the pointers are 16-byte aligned). All reductions run in a fixed order
+ * without atomics: the same inputs give bit-identical outputs from call to call.
+ */
+size_t qst_mnrl_workspace_bytes(int B, int N, int D);
+int qst_mnrl_loss(const float* a, const float* c, int B, int N, int D, int sim, float scale, int symmetric,
+                  float* out_loss, const float* grad_out, float* grad_a, float* grad_c,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_grad_norm) + torch.optim.AdamW.step()
  * with ST fit()'s two parameter groups (/root/reference/training/main.py:128-148).
  *   n            : arena elements; decay is applied per segment as the layout says

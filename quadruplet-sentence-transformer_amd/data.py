@@ -7,6 +7,7 @@ examples of similar length: the reference's `DataLoader(dataset, shuffle=True, b
 with fit() and smart_batching_collate unchanged."""
 from __future__ import annotations
 
+import random
 from typing import Iterator, List, Sequence
 
 import numpy as np
@@ -58,3 +59,48 @@ def padded_tokens(lengths: Sequence[int], batches: Sequence[Sequence[int]], mult
     """Encoder token rows a list of batches costs: per batch, size x the longest example rounded up to `multiple`."""
     L = np.asarray(lengths)
     return int(sum(len(b) * (-(-int(L[list(b)].max()) // multiple) * multiple) for b in batches if len(b)))
+
+
+class NoDuplicatesDataLoader:
+    """sentence-transformers 2.2.2's `datasets.NoDuplicatesDataLoader`: batches of `batch_size` examples in which no text
+    appears twice (compared stripped and lower-cased, over every text column), as the in-batch-negatives losses need -- a
+    text that is the positive of one anchor and sits in the batch a second time would be scored as a negative of itself.
+
+    The examples are shuffled in place once, then walked with a pointer that persists across epochs: an example whose texts
+    collide with the batch being filled is passed over for this batch (it comes round again on the next lap), and at the
+    end of the list the pointer wraps to the start after a reshuffle. `len()` is floor(len(examples) / batch_size);
+    `collate_fn` is an attribute fit() sets. Where sentence-transformers would spin for ever -- fewer distinct examples
+    than one batch needs -- a lap that adds nothing raises ValueError."""
+
+    def __init__(self, train_examples, batch_size: int):
+        if batch_size <= 0:
+            raise ValueError("batch_size must be positive")
+        self.batch_size = int(batch_size)
+        self.data_pointer = 0
+        self.collate_fn = None
+        self.train_examples = train_examples
+        random.shuffle(self.train_examples)
+
+    def __len__(self) -> int:
+        return len(self.train_examples) // self.batch_size
+
+    def __iter__(self):
+        n = len(self.train_examples)
+        for _ in range(len(self)):
+            batch, seen, idle = [], set(), 0
+            while len(batch) < self.batch_size:
+                example = self.train_examples[self.data_pointer]
+                keys = [t.strip().lower() for t in example.texts]
+                if not any(k in seen for k in keys):
+                    batch.append(example)
+                    seen.update(keys)
+                    idle = 0
+                else:
+                    idle += 1
+                    if idle > n:
+                        raise ValueError(f"NoDuplicatesDataLoader: no {self.batch_size} examples without a repeated text")
+                self.data_pointer += 1
+                if self.data_pointer >= n:
+                    self.data_pointer = 0
+                    random.shuffle(self.train_examples)
+            yield self.collate_fn(batch) if self.collate_fn is not None else batch

@@ -15,6 +15,14 @@ A distance metric given as a member of the two metric classes maps to the kernel
 Data parallel and use_amp need nothing here (fit() shards the batch and scales the loss). Under `split_batch`
 `OnlineContrastiveLoss` selects its hard pairs among the rows of each rank, as sentence-transformers under
 DistributedDataParallel does too.
+
+`MultipleNegativesRankingLoss` and `MultipleNegativesSymmetricRankingLoss` (in-batch negatives) are not row-wise: every
+anchor is scored against every candidate of the batch, by qst_mnrl_loss (csrc/mnrl.hip) -- score matrix, softmax, loss and
+both gradients in fp32. `similarity_fct` is recognised by identity: `util.cos_sim` and `util.dot_score` of this package
+(the objects the drop-in `sentence_transformers.util` re-exports) run in the kernels; any other callable is called as
+`similarity_fct(a, c) -> [B, N]` and the cross entropy runs in torch. Under `split_batch` the negatives of a rank are the
+rows of its own shard, as with sentence-transformers under DistributedDataParallel: embeddings are not gathered across
+ranks. `data.NoDuplicatesDataLoader` is the loader these losses are meant to be fed by.
 """
 from __future__ import annotations
 
@@ -23,13 +31,15 @@ from typing import Dict, Iterable, List, Optional
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, util
 from .sentence_transformer import encode_columns_fused
 
 # include/qst.h
 METRIC_COS_SIM, METRIC_COS_DIST, METRIC_L2, METRIC_L1, METRIC_DOT, METRIC_L2_PLAIN, METRIC_L1_PLAIN = range(7)
 PAIR_MSE, PAIR_CONTRASTIVE, PAIR_ONLINE_CONTRASTIVE = range(3)
 _RED_CODE = {"none": 0, "sum": 1, "mean": 2}
+SCORE_DOT, SCORE_COS = 0, 1                       # QST_SCORE_*: what qst_mnrl_loss takes as `sim`
+_SIM_CODE = {"dot": SCORE_DOT, "cos": SCORE_COS, SCORE_DOT: SCORE_DOT, SCORE_COS: SCORE_COS}
 
 
 # ------------------------------------------------------------------ direct calls (contiguous fp32 HIP tensors [B, D])
@@ -77,6 +87,23 @@ def triplet_loss_raw(a, p, n, metric: int, margin: float, reduction: int,
         _lib.check(lib.qst_triplet_loss(a.data_ptr(), p.data_ptr(), n.data_ptr(), B, D, int(metric), float(margin),
                                         int(reduction), out.data_ptr(), _lib.ptr(grad_out), *[_lib.ptr(g) for g in grads],
                                         scratch.data_ptr(), _lib.current_stream_ptr()), "qst_triplet_loss")
+    return out, grads
+
+
+def mnrl_loss_raw(a, c, sim, scale: float, symmetric: bool, grad_out: Optional[torch.Tensor] = None,
+                  want_grads: bool = False):
+    """qst_mnrl_loss on contiguous fp32 HIP tensors a [B, D], c [N, D] (sim "cos" / "dot" or SCORE_*): the loss [1] and,
+    with want_grads, [grad_a, grad_c] times grad_out (a device scalar; None = 1)."""
+    lib = _lib.load()
+    (B, D), N = a.shape, c.shape[0]
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    grads = [torch.empty_like(a), torch.empty_like(c)] if want_grads else [None, None]
+    nbytes = int(lib.qst_mnrl_workspace_bytes(B, N, D))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.qst_mnrl_loss(a.data_ptr(), c.data_ptr(), B, N, D, _SIM_CODE[sim], float(scale), int(bool(symmetric)),
+                                     out.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grads[0]), _lib.ptr(grads[1]),
+                                     ws.data_ptr(), nbytes, _lib.current_stream_ptr()), "qst_mnrl_loss")
     return out, grads
 
 
@@ -137,6 +164,21 @@ class _TripletLossFn(torch.autograd.Function):
         return (*[g.to(dt) for g, dt in zip(grads, ctx.in_dtypes)], None, None, None)
 
 
+class _MnrlFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, c, sim, scale, symmetric):
+        xs = _f32((a, c))
+        out, _ = mnrl_loss_raw(xs[0], xs[1], sim, scale, symmetric)
+        ctx.save_for_backward(*xs)
+        ctx.hp, ctx.in_dtypes = (sim, scale, symmetric), (a.dtype, c.dtype)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        _, grads = mnrl_loss_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
+        return grads[0].to(ctx.in_dtypes[0]), grads[1].to(ctx.in_dtypes[1]), None, None, None
+
+
 def _require_rows(what: str, *xs) -> None:
     if any(x.dim() != 2 for x in xs) or any(x.shape != xs[0].shape for x in xs):
         raise ValueError(f"{what}: the embeddings must all have the same shape (B, D)")
@@ -172,6 +214,25 @@ def triplet_loss(anchor, pos, neg, metric: int = METRIC_L2, margin: float = 5.0,
         raise ValueError(f"margin must not be negative, {margin} given")
     _require_rows("triplet_loss", anchor, pos, neg)
     return _TripletLossFn.apply(anchor, pos, neg, int(metric), float(margin), _RED_CODE[reduction])
+
+
+def multiple_negatives_ranking_loss(a: torch.Tensor, c: torch.Tensor, scale: float = 20.0, sim: str = "cos",
+                                    symmetric: bool = False) -> torch.Tensor:
+    """F.cross_entropy(scale * sim(a, c), arange(B)) of anchors a [B, D] and candidates c [N, D], N >= B (candidate i is
+    the positive of anchor i, the rows from B on are further negatives); `symmetric` adds the cross entropy of the
+    transposed B x B block and halves the sum. One qst_mnrl_loss call, differentiable in a and c."""
+    if sim not in ("cos", "dot"):
+        raise ValueError(f"sim is 'cos' or 'dot', {sim!r} given")
+    if not (scale > 0 and scale < float("inf")):
+        raise ValueError(f"scale must be positive and finite, {scale} given")
+    if a.dim() != 2 or c.dim() != 2 or a.shape[1] != c.shape[1] or a.shape[1] < 1:
+        raise ValueError("multiple_negatives_ranking_loss: anchors (B, D) and candidates (N, D) must share D >= 1")
+    if a.shape[0] < 1 or c.shape[0] < a.shape[0]:
+        raise ValueError(f"multiple_negatives_ranking_loss: {a.shape[0]} anchors need at least as many candidates, "
+                         f"{c.shape[0]} given")
+    if not (a.is_cuda and c.is_cuda):
+        raise _lib.QstError("multiple_negatives_ranking_loss runs on the HIP device only (inputs are CPU tensors; no CPU path)")
+    return _MnrlFn.apply(a, c, sim, float(scale), bool(symmetric))
 
 
 def quadruplet_eval_raw(a, p, q, n, want_dist: bool = False):
@@ -349,3 +410,53 @@ class TripletLoss(_TupleLoss):
         if code is not None:
             return triplet_loss(a, p, n, code, self.triplet_margin, "mean")
         return torch.relu(self.distance_metric(a, p) - self.distance_metric(a, n) + self.triplet_margin).mean()
+
+
+class MultipleNegativesRankingLoss(_TupleLoss):
+    """F.cross_entropy(scale * similarity_fct(anchors, candidates), arange(B)): each example is (anchor, positive[, hard
+    negatives ...]); the candidates of anchor i are the positives of the whole batch followed by all its hard negatives,
+    and candidate i is the right answer. Takes 2 or more text columns. With `util.cos_sim` (the default) or
+    `util.dot_score` the whole loss and its gradients are one qst_mnrl_loss call; any other callable is called as
+    `similarity_fct(a, c) -> [B, N]` and the cross entropy runs in torch. `labels` is not looked at, as in
+    sentence-transformers -- but fit() skips a step whose labels tensor is empty, so the examples keep InputExample's
+    default label. Feed it from `NoDuplicatesDataLoader`: a text that appears twice in a batch is its own false negative."""
+    reduction = "mean"
+    _symmetric = False
+
+    def __init__(self, model, scale: float = 20.0, similarity_fct=util.cos_sim, fused: bool = True):
+        super().__init__(model, fused)
+        self.scale = scale
+        self.similarity_fct = similarity_fct
+
+    def get_config_dict(self):
+        return {"scale": self.scale, "similarity_fct": self.similarity_fct.__name__}
+
+    def _kernel_sim(self) -> Optional[str]:
+        if self.similarity_fct is util.cos_sim:
+            return "cos"
+        if self.similarity_fct is util.dot_score:
+            return "dot"
+        return None
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor = None) -> torch.Tensor:
+        cols = list(sentence_features)
+        if len(cols) < 2:
+            raise ValueError(f"{type(self).__name__} takes 2 or more text columns per example, {len(cols)} given")
+        reps = self._embed(cols, len(cols))
+        a = reps[0]
+        c = reps[1] if len(reps) == 2 else torch.cat(reps[1:], 0)
+        sim = self._kernel_sim()
+        if sim is not None:
+            return multiple_negatives_ranking_loss(a, c, self.scale, sim, self._symmetric)
+        scores = self.similarity_fct(a, c) * self.scale
+        target = torch.arange(scores.shape[0], device=scores.device)
+        loss = torch.nn.functional.cross_entropy(scores, target)
+        if self._symmetric:
+            loss = (loss + torch.nn.functional.cross_entropy(scores[:, :scores.shape[0]].t(), target)) / 2
+        return loss
+
+
+class MultipleNegativesSymmetricRankingLoss(MultipleNegativesRankingLoss):
+    """MultipleNegativesRankingLoss plus the same question asked the other way round -- given positive i, find anchor i among
+    the anchors of the batch (the transposed B x B block of the scores) -- and the two halved."""
+    _symmetric = True
