@@ -307,6 +307,36 @@ int qst_mnrl_loss(const float* a, const float* c, int B, int N, int D, int sim, 
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The batch-mining triplet losses of sentence-transformers 2.2.2 (version 106; csrc/batch_triplet.hip): BatchHardTripletLoss,
+ * BatchHardSoftMarginTripletLoss, BatchSemiHardTripletLoss, BatchAllTripletLoss. x fp32 [B, D], rows contiguous; labels
+ * int64 [B]. d [B, B] is the distance of every pair of rows: metric QST_METRIC_L2_PLAIN (sqrt(sum_k (x_ik - x_jk)^2); bit-identical
+ * rows give 0, and an exactly-zero distance passes no gradient) or QST_METRIC_COS_DIST (1 - <x_hat_i, x_hat_j>, x_hat =
+ * F.normalize(x, p=2, dim=1, eps=1e-12), the gradient through the normalisation as qst_mnrl_loss). pos[i, j]: labels equal
+ * and i != j; neg[i, k]: labels differ. With m = margin:
+ *   QST_BT_HARD       hp_i = max_j(pos[i, j] * d_ij) (0 without a positive), hn_i = min_k(d_ik + max_k'(d_ik') * (1 - neg[i, k]));
+ *                     mean_i relu(hp_i - hn_i + m)
+ *   QST_BT_HARD_SOFT  the same hp, hn; mean_i log1p(exp(hp_i - hn_i)); margin is checked and not used
+ *   QST_BT_ALL        sum over pos[i, j] & neg[i, k] of t = relu(d_ij - d_ik + m), / (#{t > 1e-16} + 1e-16)
+ *   QST_BT_SEMIHARD   per pair pos[i, j]: n_ij = min{d_ik : neg[i, k], d_ik > d_ij}; if that set is empty the largest d_ik
+ *                     over neg[i, k]; if anchor i has no negative the smallest entry of row i (its diagonal).
+ *                     sum relu(d_ij - n_ij + m) / #pairs; a batch without any pair gives 0 / 0 = NaN, as upstream does
+ * A max or min passes its gradient to the selected element only (the smallest index among equal values).
+ * out_loss fp32 [1]. out_counts int64 [2] or NULL: {terms of the denominator's population, terms > 0} -- hard {B, anchors
+ * with a positive hinge}, soft {B, B}, all {valid triplets, triplets > 1e-16}, semi {pairs, pairs with a positive hinge}.
+ * grad_x fp32 [B, D] or NULL = forward only. grad_out: fp32 [1] on the DEVICE (NULL = 1), read by the kernels -- no host
+ * synchronisation, capturable in a HIP graph; it multiplies the finished gradient. No atomics, every reduction in a fixed
+ * order: the same inputs give bit-identical outputs from call to call.
+ * B < 1, D < 1, a NULL x, labels, out_loss or workspace, a workspace smaller than qst_batch_triplet_workspace_bytes(B, D) or
+ * not 16-byte aligned, another kind or metric, a margin that is negative or not finite: QST_ERR_BAD_ARG before any launch,
+ * nothing written. B * ldB (ldB = B rounded up to 4) or B * D past 2^31 - 1: QST_ERR_UNSUPPORTED.
+ */
+enum { QST_BT_HARD = 0, QST_BT_HARD_SOFT = 1, QST_BT_SEMIHARD = 2, QST_BT_ALL = 3 };
+size_t qst_batch_triplet_workspace_bytes(int B, int D);
+int qst_batch_triplet_loss(const float* x, const int64_t* labels, int B, int D, int kind, int metric, float margin,
+                           float* out_loss, int64_t* out_counts /* [2] or NULL */, const float* grad_out,
+                           float* grad_x /* NULL = forward only */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_grad_norm) + torch.optim.AdamW.step()
  * with ST fit()'s two parameter groups (/root/reference/training/main.py:128-148).
  *   n            : arena elements; decay is applied per segment as the layout says

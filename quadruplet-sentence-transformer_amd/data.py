@@ -11,6 +11,7 @@ import random
 from typing import Iterator, List, Sequence
 
 import numpy as np
+from torch.utils.data import IterableDataset
 
 
 class LengthBucketBatchSampler:
@@ -104,3 +105,54 @@ class NoDuplicatesDataLoader:
                     self.data_pointer = 0
                     random.shuffle(self.train_examples)
             yield self.collate_fn(batch) if self.collate_fn is not None else batch
+
+
+class SentenceLabelDataset(IterableDataset):
+    """sentence-transformers 2.2.2's `datasets.SentenceLabelDataset`: the examples (one text, one integer label each) in
+    runs of `samples_per_label` consecutive examples of one label, so that every batch cut from the stream --
+    `DataLoader(SentenceLabelDataset(examples), batch_size=...)`, batch_size a multiple of samples_per_label -- holds
+    positives for the batch-mining triplet losses.
+
+    Labels with fewer than `samples_per_label` examples are dropped; `len()` is the number of examples kept. One pass
+    yields whole runs until `len()` examples have gone out (the last run is not cut short). The labels are visited in a
+    shuffled order; within a lap an example is not drawn twice unless `with_replacement`; a label with too few unseen
+    examples left is passed over, and when the labels are exhausted the order is reshuffled and every example is unseen
+    again. Draws come from numpy's global generator."""
+
+    def __init__(self, examples, samples_per_label: int = 2, with_replacement: bool = False):
+        super().__init__()
+        if samples_per_label < 1:
+            raise ValueError("samples_per_label must be positive")
+        self.samples_per_label = int(samples_per_label)
+        self.with_replacement = bool(with_replacement)
+        by_label = {}
+        for example in examples:
+            by_label.setdefault(example.label, []).append(example)
+        self.grouped_inputs, self.groups_right_border = [], []      # the kept examples label by label; where each group ends
+        for group in by_label.values():
+            if len(group) >= self.samples_per_label:
+                self.grouped_inputs.extend(group)
+                self.groups_right_border.append(len(self.grouped_inputs))
+        self.label_range = np.arange(len(self.groups_right_border))
+        np.random.shuffle(self.label_range)
+
+    def __len__(self) -> int:
+        return len(self.grouped_inputs)
+
+    def __iter__(self):
+        n_labels = len(self.label_range)
+        at, count, seen = 0, 0, {}
+        while count < len(self.grouped_inputs):
+            group = int(self.label_range[at])
+            lo = self.groups_right_border[group - 1] if group > 0 else 0
+            mine = seen.setdefault(group, set())
+            pool = [i for i in range(lo, self.groups_right_border[group]) if self.with_replacement or i not in mine]
+            if len(pool) >= self.samples_per_label:
+                for i in np.random.choice(pool, self.samples_per_label, replace=False):
+                    count += 1
+                    mine.add(int(i))
+                    yield self.grouped_inputs[int(i)]
+            at += 1
+            if at >= n_labels:
+                at, seen = 0, {}
+                np.random.shuffle(self.label_range)

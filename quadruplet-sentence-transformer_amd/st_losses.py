@@ -23,6 +23,15 @@ both gradients in fp32. `similarity_fct` is recognised by identity: `util.cos_si
 `similarity_fct(a, c) -> [B, N]` and the cross entropy runs in torch. Under `split_batch` the negatives of a rank are the
 rows of its own shard, as with sentence-transformers under DistributedDataParallel: embeddings are not gathered across
 ranks. `data.NoDuplicatesDataLoader` is the loader these losses are meant to be fed by.
+
+`BatchHardTripletLoss`, `BatchHardSoftMarginTripletLoss`, `BatchSemiHardTripletLoss` and `BatchAllTripletLoss` take ONE text
+column and an integer class label per example, and mine their triplets among the B x B distances of the batch at every
+step: distance matrix, mining, loss and the gradient through the selections are qst_batch_triplet_loss
+(csrc/batch_triplet.hip), fp32, without atomics. `distance_metric` is one of the two members of
+`BatchHardTripletLossDistanceFunction` (recognised by their tag: they run in the kernels); any other callable is called as
+`f(embeddings) -> [B, B]` and the mining runs in torch on its result -- `eucledian_distance` with `squared=True` goes that
+way. `data.SentenceLabelDataset` is the loader they are meant to be fed by. Under `split_batch` rank r mines among rows
+r::world of the batch only, so `samples_per_label` must be at least 2 * world for a rank to see a positive.
 """
 from __future__ import annotations
 
@@ -40,6 +49,7 @@ PAIR_MSE, PAIR_CONTRASTIVE, PAIR_ONLINE_CONTRASTIVE = range(3)
 _RED_CODE = {"none": 0, "sum": 1, "mean": 2}
 SCORE_DOT, SCORE_COS = 0, 1                       # QST_SCORE_*: what qst_mnrl_loss takes as `sim`
 _SIM_CODE = {"dot": SCORE_DOT, "cos": SCORE_COS, SCORE_DOT: SCORE_DOT, SCORE_COS: SCORE_COS}
+BT_HARD, BT_HARD_SOFT, BT_SEMIHARD, BT_ALL = range(4)      # QST_BT_*: what qst_batch_triplet_loss takes as `kind`
 
 
 # ------------------------------------------------------------------ direct calls (contiguous fp32 HIP tensors [B, D])
@@ -105,6 +115,25 @@ def mnrl_loss_raw(a, c, sim, scale: float, symmetric: bool, grad_out: Optional[t
                                      out.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grads[0]), _lib.ptr(grads[1]),
                                      ws.data_ptr(), nbytes, _lib.current_stream_ptr()), "qst_mnrl_loss")
     return out, grads
+
+
+def batch_triplet_loss_raw(x, labels, kind: int, metric: int, margin: float, grad_out: Optional[torch.Tensor] = None,
+                           want_grads: bool = False):
+    """qst_batch_triplet_loss on a contiguous fp32 HIP tensor x [B, D] and contiguous int64 HIP labels [B] (kind BT_*,
+    metric METRIC_L2_PLAIN or METRIC_COS_DIST): the loss [1], the gradient [B, D] times grad_out (a device scalar; None = 1)
+    or None, and the counts int64 [2] = {terms the denominator is drawn from, terms > 0}."""
+    lib = _lib.load()
+    B, D = x.shape
+    out = torch.empty(1, dtype=torch.float32, device=x.device)
+    counts = torch.empty(2, dtype=torch.int64, device=x.device)
+    grad = torch.empty_like(x) if want_grads else None
+    nbytes = int(lib.qst_batch_triplet_workspace_bytes(B, D))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.qst_batch_triplet_loss(x.data_ptr(), labels.data_ptr(), B, D, int(kind), int(metric), float(margin),
+                                              out.data_ptr(), counts.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grad),
+                                              ws.data_ptr(), nbytes, _lib.current_stream_ptr()), "qst_batch_triplet_loss")
+    return out, grad, counts
 
 
 # ------------------------------------------------------------------ autograd (save the inputs, recompute in backward)
@@ -179,6 +208,23 @@ class _MnrlFn(torch.autograd.Function):
         return grads[0].to(ctx.in_dtypes[0]), grads[1].to(ctx.in_dtypes[1]), None, None, None
 
 
+class _BatchTripletFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, labels, kind, metric, margin):
+        (x32,) = _f32((x,))
+        y = labels.detach().to(torch.int64).contiguous().reshape(-1)
+        out, _, _ = batch_triplet_loss_raw(x32, y, kind, metric, margin)
+        ctx.save_for_backward(x32, y)
+        ctx.hp, ctx.in_dtype = (kind, metric, margin), x.dtype
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        x32, y = ctx.saved_tensors
+        _, grad, _ = batch_triplet_loss_raw(x32, y, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
+        return grad.to(ctx.in_dtype), None, None, None, None
+
+
 def _require_rows(what: str, *xs) -> None:
     if any(x.dim() != 2 for x in xs) or any(x.shape != xs[0].shape for x in xs):
         raise ValueError(f"{what}: the embeddings must all have the same shape (B, D)")
@@ -233,6 +279,29 @@ def multiple_negatives_ranking_loss(a: torch.Tensor, c: torch.Tensor, scale: flo
     if not (a.is_cuda and c.is_cuda):
         raise _lib.QstError("multiple_negatives_ranking_loss runs on the HIP device only (inputs are CPU tensors; no CPU path)")
     return _MnrlFn.apply(a, c, sim, float(scale), bool(symmetric))
+
+
+def batch_triplet_loss(x: torch.Tensor, labels: torch.Tensor, kind: int = BT_HARD, metric: int = METRIC_L2_PLAIN,
+                       margin: float = 5.0) -> torch.Tensor:
+    """One of the four batch-mining triplet losses (kind BT_HARD, BT_HARD_SOFT, BT_SEMIHARD, BT_ALL) of embeddings x [B, D]
+    with one integer class label per row, under METRIC_L2_PLAIN (eucledian_distance) or METRIC_COS_DIST (cosine_distance).
+    One qst_batch_triplet_loss call, differentiable in x. BT_HARD_SOFT takes no margin. BT_SEMIHARD is NaN for a batch in
+    which no label occurs twice, as in sentence-transformers."""
+    if kind not in (BT_HARD, BT_HARD_SOFT, BT_SEMIHARD, BT_ALL):
+        raise ValueError(f"kind is one of BT_HARD, BT_HARD_SOFT, BT_SEMIHARD, BT_ALL (0 .. 3), {kind!r} given")
+    if metric not in (METRIC_L2_PLAIN, METRIC_COS_DIST):
+        raise ValueError(f"metric is METRIC_L2_PLAIN or METRIC_COS_DIST, {metric!r} given")
+    if not (margin >= 0 and margin < float("inf")):
+        raise ValueError(f"margin must be finite and not negative, {margin} given")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("batch_triplet_loss: the embeddings must have the shape (B, D), B >= 1, D >= 1")
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.is_complex():
+        raise ValueError(f"batch_triplet_loss: the labels are integer class ids, {labels.dtype} given")
+    if labels.numel() != x.shape[0]:
+        raise ValueError(f"batch_triplet_loss: {x.shape[0]} rows but {labels.numel()} labels")
+    _require_rows("batch_triplet_loss", x)
+    _require_labels("batch_triplet_loss", labels, x.shape[0])
+    return _BatchTripletFn.apply(x, labels, int(kind), int(metric), float(margin))
 
 
 def quadruplet_eval_raw(a, p, q, n, want_dist: bool = False):
@@ -460,3 +529,130 @@ class MultipleNegativesSymmetricRankingLoss(MultipleNegativesRankingLoss):
     """MultipleNegativesRankingLoss plus the same question asked the other way round -- given positive i, find anchor i among
     the anchors of the batch (the transposed B x B block of the scores) -- and the two halved."""
     _symmetric = True
+
+
+# ------------------------------------------------------------------ the batch-mining triplet losses
+class BatchHardTripletLossDistanceFunction:
+    """The distance of every pair of rows of the batch, `f(embeddings) -> [B, B]`. The members carry the kernel's metric
+    code: given to one of the four losses below as they are, they run inside qst_batch_triplet_loss; called directly they
+    are sentence-transformers' torch formulas, on any device and differentiable."""
+
+    @staticmethod
+    def cosine_distance(embeddings):
+        """1 - cos_sim(embeddings, embeddings)"""
+        e = torch.nn.functional.normalize(embeddings, p=2, dim=1, eps=1e-12)
+        return 1 - e @ e.t()
+
+    @staticmethod
+    def eucledian_distance(embeddings, squared=False):
+        """||a - b||_2 (squared: its square) from the Gram matrix, clamped at 0; an exactly-zero distance has gradient 0."""
+        dot_product = embeddings @ embeddings.t()
+        square_norm = torch.diag(dot_product)
+        distances = (square_norm.unsqueeze(0) - 2.0 * dot_product + square_norm.unsqueeze(1)).clamp_min(0)
+        if not squared:
+            mask = distances.eq(0).to(distances.dtype)
+            distances = (1.0 - mask) * torch.sqrt(distances + mask * 1e-16)
+        return distances
+
+
+BatchHardTripletLossDistanceFunction.cosine_distance._qst_metric = METRIC_COS_DIST
+BatchHardTripletLossDistanceFunction.eucledian_distance._qst_metric = METRIC_L2_PLAIN
+
+
+def _masked_minimum(data, mask, dim=1):
+    axis_maximums = data.max(dim, keepdim=True)[0]
+    return ((data - axis_maximums) * mask).min(dim, keepdim=True)[0] + axis_maximums
+
+
+def _masked_maximum(data, mask, dim=1):
+    axis_minimums = data.min(dim, keepdim=True)[0]
+    return ((data - axis_minimums) * mask).max(dim, keepdim=True)[0] + axis_minimums
+
+
+def batch_triplet_mining_torch(d: torch.Tensor, labels: torch.Tensor, kind: int, margin: float) -> torch.Tensor:
+    """The mining of the four losses in sentence-transformers' tensor formulation, on a distance matrix d [B, B] that is
+    already there: what a `distance_metric` the kernels do not know is followed by."""
+    labels = labels.view(-1)
+    B = labels.numel()
+    same = labels.unsqueeze(0) == labels.unsqueeze(1)
+    eye = torch.eye(B, dtype=torch.bool, device=d.device)
+    pos, neg = (same & ~eye).to(d.dtype), (~same).to(d.dtype)
+    if kind in (BT_HARD, BT_HARD_SOFT):
+        hardest_positive = (pos * d).max(1, keepdim=True)[0]
+        hardest_negative = (d + d.max(1, keepdim=True)[0] * (1.0 - neg)).min(1, keepdim=True)[0]
+        if kind == BT_HARD_SOFT:
+            return torch.log1p(torch.exp(hardest_positive - hardest_negative)).mean()
+        return torch.relu(hardest_positive - hardest_negative + margin).mean()
+    if kind == BT_ALL:
+        t = d.unsqueeze(2) - d.unsqueeze(1) + margin
+        t = torch.relu((pos.unsqueeze(2) * neg.unsqueeze(1)) * t)
+        return t.sum() / ((t > 1e-16).sum().to(d.dtype) + 1e-16)
+    if kind != BT_SEMIHARD:
+        raise ValueError(f"kind is one of BT_HARD, BT_HARD_SOFT, BT_SEMIHARD, BT_ALL (0 .. 3), {kind!r} given")
+    tile = d.repeat(B, 1)                                           # row j * B + i holds d[i, :]
+    mask = (~same).repeat(B, 1) & (tile > d.t().reshape(-1, 1))     # ... and asks for the negatives farther than d[i, j]
+    mask_final = (mask.sum(1, keepdim=True) > 0).reshape(B, B).t()
+    negatives_outside = _masked_minimum(tile, mask.to(d.dtype)).reshape(B, B).t()
+    negatives_inside = _masked_maximum(d, neg).repeat(1, B)
+    semi_hard_negatives = torch.where(mask_final, negatives_outside, negatives_inside)
+    loss_mat = d - semi_hard_negatives + margin
+    return torch.relu(loss_mat * pos).sum() / pos.sum()
+
+
+class _BatchTripletLoss(_TupleLoss):
+    reduction = "mean"
+    _kind = BT_HARD
+
+    def __init__(self, model, distance_metric=BatchHardTripletLossDistanceFunction.eucledian_distance, margin: float = 5,
+                 fused: bool = True):
+        super().__init__(model, fused)
+        self.distance_metric = distance_metric
+        self.triplet_margin = margin
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor) -> torch.Tensor:
+        (rep,) = self._embed(sentence_features, 1)
+        return self._loss(labels, rep)
+
+    def _loss(self, labels: torch.Tensor, embeddings: torch.Tensor) -> torch.Tensor:
+        code = getattr(self.distance_metric, "_qst_metric", None)
+        if code is not None:
+            return batch_triplet_loss(embeddings, labels, self._kind, code, self.triplet_margin)
+        return batch_triplet_mining_torch(self.distance_metric(embeddings), labels, self._kind, self.triplet_margin)
+
+
+class BatchHardTripletLoss(_BatchTripletLoss):
+    """mean over the anchors of relu(hardest positive - hardest negative + margin): per anchor the farthest row of its own
+    label and the closest row of another, mined among the rows of the batch (one text column, integer class labels)."""
+    _kind = BT_HARD
+
+    def batch_hard_triplet_loss(self, labels: torch.Tensor, embeddings: torch.Tensor) -> torch.Tensor:
+        return self._loss(labels, embeddings)
+
+
+class BatchHardSoftMarginTripletLoss(_BatchTripletLoss):
+    """BatchHardTripletLoss with the soft margin log1p(exp(hardest positive - hardest negative)) in place of the hinge."""
+    _kind = BT_HARD_SOFT
+
+    def __init__(self, model, distance_metric=BatchHardTripletLossDistanceFunction.eucledian_distance, fused: bool = True):
+        super().__init__(model, distance_metric, 0.0, fused)
+
+    def batch_hard_triplet_soft_margin_loss(self, labels: torch.Tensor, embeddings: torch.Tensor) -> torch.Tensor:
+        return self._loss(labels, embeddings)
+
+
+class BatchSemiHardTripletLoss(_BatchTripletLoss):
+    """Per pair (anchor, positive) the closest negative that is farther away than the positive; if there is none, the
+    farthest negative. Mean over the pairs of relu(d(a, p) - d(a, n) + margin). A batch in which no label occurs twice has
+    no pair and gives NaN, as in sentence-transformers: feed it from SentenceLabelDataset."""
+    _kind = BT_SEMIHARD
+
+    def batch_semi_hard_triplet_loss(self, labels: torch.Tensor, embeddings: torch.Tensor) -> torch.Tensor:
+        return self._loss(labels, embeddings)
+
+
+class BatchAllTripletLoss(_BatchTripletLoss):
+    """relu(d(a, p) - d(a, n) + margin) over every valid triplet of the batch, averaged over those that are positive."""
+    _kind = BT_ALL
+
+    def batch_all_triplet_loss(self, labels: torch.Tensor, embeddings: torch.Tensor) -> torch.Tensor:
+        return self._loss(labels, embeddings)
