@@ -1,6 +1,8 @@
 from quadruplet_sentence_transformer_amd.evaluation import (EmbeddingSimilarityEvaluator,  # noqa: F401
-                                                            InformationRetrievalEvaluator, ParaphraseMiningEvaluator,
+                                                            InformationRetrievalEvaluator, MSEEvaluator,
+                                                            ParaphraseMiningEvaluator,
                                                             QuadrupletEvaluator,
                                                             QuadrupletLossEvaluator, SentenceEvaluator,
-                                                            SequentialEvaluator, SimilarityFunction, TripletEvaluator,
+                                                            SequentialEvaluator, SimilarityFunction, TranslationEvaluator,
+                                                            TripletEvaluator,
                                                             get_sequential_evaluator)

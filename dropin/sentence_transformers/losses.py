@@ -1,8 +1,9 @@
-"""sentence_transformers.losses: the pair, triplet, in-batch-negatives and batch-mining triplet objectives on the HIP path (st_losses.py)."""
+"""sentence_transformers.losses: the pair, triplet, in-batch-negatives, batch-mining triplet and distillation objectives on the HIP
+path (st_losses.py)."""
 from quadruplet_sentence_transformer_amd.st_losses import (BatchAllTripletLoss, BatchHardSoftMarginTripletLoss,  # noqa: F401
                                                            BatchHardTripletLoss, BatchHardTripletLossDistanceFunction,
                                                            BatchSemiHardTripletLoss, ContrastiveLoss, CosineSimilarityLoss,
-                                                           MultipleNegativesRankingLoss,
+                                                           MarginMSELoss, MSELoss, MultipleNegativesRankingLoss,
                                                            MultipleNegativesSymmetricRankingLoss,
                                                            OnlineContrastiveLoss, SiameseDistanceMetric,
                                                            TripletDistanceMetric, TripletLoss)

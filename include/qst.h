@@ -337,6 +337,36 @@ int qst_batch_triplet_loss(const float* x, const int64_t* labels, int B, int D, 
                            float* grad_x /* NULL = forward only */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Distillation from a teacher, sentence-transformers 2.2.2 (version 107; csrc/distill.hip): losses.MSELoss and what
+ * evaluation.MSEEvaluator scores with, and losses.MarginMSELoss. All tensors fp32, rows contiguous (stride D); any B >= 1 and
+ * D >= 1 (16-byte accesses when D % 4 == 0 and the pointers are 16-byte aligned, element by element otherwise; rows are kept
+ * in registers up to D = 2048 and read a second time by the gradient pass beyond). Both run on the caller's stream without
+ * host synchronisation (capturable in a HIP graph), grad_out is read on the device, and it multiplies the finished
+ * gradient: a call with grad_out = g returns the correctly rounded g * (the gradients without). No atomics: the per-row
+ * values go through a one-workgroup second stage that sums them in double in a fixed order, so the same inputs give
+ * bit-identical outputs from call to call.
+ * B < 1, D < 1, a NULL input or out_loss, a NULL scratch where one is needed, another sim or reduction: QST_ERR_BAD_ARG before
+ * any launch, nothing written.
+ */
+/* mean over all B*D elements of (x - t)^2   (torch.nn.MSELoss() on [B, D]; MSELoss, MSEEvaluator)
+ * out_loss fp32 [1]. grad_x fp32 [B, D] or NULL = forward only (nothing else is written):
+ *   grad_out * 2 * (x - t) / (B * D), grad_out fp32 [1] on the DEVICE (NULL = 1), multiplying the finished gradient.
+ * scratch fp32 [B]. */
+int qst_embed_mse(const float* x, const float* t, int B, int D, float* out_loss,
+                  const float* grad_out, float* grad_x, float* scratch, void* stream);
+/* m_b = sim(q_b, p_b) - sim(q_b, n_b); row_b = (m_b - labels_b)^2; reduction QST_REDUCE_NONE / SUM / MEAN as qst_triplet_loss
+ * (grad_out [B] for NONE, [1] otherwise, NULL = ones). sim: QST_METRIC_DOT or QST_METRIC_COS_SIM, the latter with exactly
+ * the semantics qst_pair_metric documents (each norm clamped at 1e-8) so that the fused and the unfused path agree.
+ * util.pairwise_cos_sim of 2.2.2 normalises each row with F.normalize (x / max(|x|_2, 1e-12)) before the dot product
+ * instead: the two differ only for rows whose norm is below 1e-8 -- here such a row is divided by 1e-8 and its norm
+ * passes no gradient, in 2.2.2 it is divided by its own norm down to 1e-12. A zero row gives 0 in both.
+ * out_margin fp32 [B] or NULL receives m. grad_q/p/n all NULL = forward only; some but not all NULL: QST_ERR_BAD_ARG.
+ * scratch fp32 [B] (may be NULL for QST_REDUCE_NONE). */
+int qst_margin_mse_loss(const float* q, const float* p, const float* n, const float* labels, int B, int D, int sim,
+                        int reduction, float* out_loss, float* out_margin, const float* grad_out,
+                        float* grad_q, float* grad_p, float* grad_n, float* scratch, void* stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_grad_norm) + torch.optim.AdamW.step()
  * with ST fit()'s two parameter groups (/root/reference/training/main.py:128-148).
  *   n            : arena elements; decay is applied per segment as the layout says

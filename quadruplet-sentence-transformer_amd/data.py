@@ -7,11 +7,14 @@ examples of similar length: the reference's `DataLoader(dataset, shuffle=True, b
 with fit() and smart_batching_collate unchanged."""
 from __future__ import annotations
 
+import gzip
 import random
 from typing import Iterator, List, Sequence
 
 import numpy as np
-from torch.utils.data import IterableDataset
+from torch.utils.data import Dataset, IterableDataset
+
+from .sentence_transformer import InputExample
 
 
 class LengthBucketBatchSampler:
@@ -156,3 +159,113 @@ class SentenceLabelDataset(IterableDataset):
             if at >= n_labels:
                 at, seen = 0, {}
                 np.random.shuffle(self.label_range)
+
+
+class ParallelSentencesDataset(Dataset):
+    """sentence-transformers 2.2.2's `datasets.ParallelSentencesDataset`, the data side of losses.MSELoss: parallel sentences
+    (a source sentence and its translations, or just the sentence itself for a plain distillation) become
+    `InputExample(texts=[sentence], label=teacher embedding of the SOURCE sentence)` -- one example for the source and one
+    for every translation, so that the student learns to put all of them where the teacher puts the source.
+
+    Several datasets can be added (`load_data` from a tab-separated file, `.gz` accepted, one source sentence followed by
+    its translations per line; `add_dataset` from lists). `generate_data` takes one entry from a dataset `weight` times for
+    every dataset -- so the datasets are drawn in proportion to their weights --, has the teacher encode the source
+    sentences in batches of `batch_size` (`teacher_model` is any object with `encode()`; with `use_embedding_cache` a
+    sentence is encoded once and its embedding kept), and shuffles the resulting examples; `__getitem__` hands them out
+    and generates the next round when they run out, whatever index is asked for. `len()` is the number of sentences
+    (sources and translations) of all datasets. A dataset is walked through in order and reshuffled when it has been
+    exhausted. Feed it through `DataLoader(dataset, shuffle=False, batch_size=...)` and fit()'s collate function.
+
+    `student_model` is kept for the signature's sake and not used, as in 2.2.2. Where this differs from 2.2.2: the
+    translations of a source keep the order in which they were first seen (2.2.2 holds them in a set, whose order changes
+    from process to process); shuffling uses the `random` module's global generator, as there."""
+
+    def __init__(self, student_model, teacher_model, batch_size: int = 8, use_embedding_cache: bool = True):
+        self.student_model = student_model
+        self.teacher_model = teacher_model
+        self.batch_size = batch_size
+        self.use_embedding_cache = use_embedding_cache
+        self.datasets = []                # per dataset: [(source, [source and its translations])]
+        self.datasets_iterator = []       # per dataset: the next entry to take
+        self.dataset_indices = []         # dataset ids, each `weight` times: one round of generate_data
+        self.cache = []                   # the examples of the current round
+        self.embedding_cache = {}
+        self.num_sentences = 0
+
+    @staticmethod
+    def _too_long(sentences, max_sentence_length) -> bool:
+        return max_sentence_length is not None and max_sentence_length > 0 and \
+            max(len(sent) for sent in sentences) > max_sentence_length
+
+    def load_data(self, filepath: str, weight: int = 100, max_sentences: int = None, max_sentence_length: int = 128):
+        """One line = the source sentence and its translations, separated by tabs. Lines with a sentence of more than
+        max_sentence_length characters are passed over; reading stops after max_sentences kept lines."""
+        parallel_sentences = []
+        opener = gzip.open if filepath.endswith(".gz") else open
+        with opener(filepath, "rt", encoding="utf8") as f:
+            for line in f:
+                sentences = line.strip().split("\t")
+                if self._too_long(sentences, max_sentence_length):
+                    continue
+                parallel_sentences.append(sentences)
+                if max_sentences is not None and 0 < max_sentences <= len(parallel_sentences):
+                    break
+        self.add_dataset(parallel_sentences, weight=weight, max_sentences=max_sentences,
+                         max_sentence_length=max_sentence_length)
+
+    def add_dataset(self, parallel_sentences: List[List[str]], weight: int = 100, max_sentences: int = None,
+                    max_sentence_length: int = 128):
+        """parallel_sentences: [[source, translation, ...], ...]. Entries with the same source are merged; at most
+        max_sentences different sources are kept."""
+        sentences_map = {}
+        for sentences in parallel_sentences:
+            if self._too_long(sentences, max_sentence_length):
+                continue
+            targets = sentences_map.setdefault(sentences[0], {})
+            for sent in sentences:
+                targets[sent] = None
+            if max_sentences is not None and 0 < max_sentences <= len(sentences_map):
+                break
+        if not sentences_map:
+            return
+        self.num_sentences += sum(len(t) for t in sentences_map.values())
+        dataset_id = len(self.datasets)
+        self.datasets.append([(src, list(t)) for src, t in sentences_map.items()])
+        self.datasets_iterator.append(0)
+        self.dataset_indices.extend([dataset_id] * weight)
+
+    def next_entry(self, data_idx: int):
+        source, targets = self.datasets[data_idx][self.datasets_iterator[data_idx]]
+        self.datasets_iterator[data_idx] += 1
+        if self.datasets_iterator[data_idx] >= len(self.datasets[data_idx]):
+            self.datasets_iterator[data_idx] = 0
+            random.shuffle(self.datasets[data_idx])
+        return source, targets
+
+    def generate_data(self):
+        entries = [self.next_entry(data_idx) for data_idx in self.dataset_indices]
+        src_embeddings = self.get_embeddings([src for src, _ in entries])
+        for src_embedding, (_, targets) in zip(src_embeddings, entries):
+            for sent in targets:
+                self.cache.append(InputExample(texts=[sent], label=src_embedding))
+        random.shuffle(self.cache)
+
+    def get_embeddings(self, sentences: List[str]):
+        """The teacher's embeddings of `sentences`, in their order."""
+        encode = lambda xs: self.teacher_model.encode(xs, batch_size=self.batch_size, show_progress_bar=False,  # noqa: E731
+                                                      convert_to_numpy=True)
+        if not self.use_embedding_cache:
+            return encode(sentences)
+        new_sentences = list(dict.fromkeys(s for s in sentences if s not in self.embedding_cache))
+        if new_sentences:
+            for sent, embedding in zip(new_sentences, encode(new_sentences)):
+                self.embedding_cache[sent] = embedding
+        return [self.embedding_cache[sent] for sent in sentences]
+
+    def __len__(self) -> int:
+        return self.num_sentences
+
+    def __getitem__(self, idx):
+        if not self.cache:
+            self.generate_data()
+        return self.cache.pop()

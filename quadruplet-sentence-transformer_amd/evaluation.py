@@ -2,8 +2,9 @@
 572-612; ir_evauation_script.py:107-131): the base class, SimilarityFunction, SequentialEvaluator, an encode()-driven
 TripletEvaluator and InformationRetrievalEvaluator, whose scoring + top-k run on the GPU
 through libqst (util.topk_scores), EmbeddingSimilarityEvaluator (graded pairs; qst_pair_metric) and
-ParaphraseMiningEvaluator (util.paraphrase_mining on the streaming top-k, qst_topk_stream). The two evaluators the
-reference selects its models with, QuadrupletEvaluator (qst_quadruplet_eval) and QuadrupletLossEvaluator, and the chain
+ParaphraseMiningEvaluator (util.paraphrase_mining on the streaming top-k, qst_topk_stream), and the two that go with a
+distillation, MSEEvaluator (qst_embed_mse) and TranslationEvaluator (two k = 1 searches of the streaming top-k). The two
+evaluators the reference selects its models with, QuadrupletEvaluator (qst_quadruplet_eval) and QuadrupletLossEvaluator, and the chain
 get_sequential_evaluator builds of them stand at the end."""
 from __future__ import annotations
 
@@ -497,6 +498,85 @@ class ParaphraseMiningEvaluator(SentenceEvaluator):
             _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers,
                         [epoch, steps, m["precision"], m["recall"], m["f1"], m["threshold"], m["average_precision"]])
         return m["average_precision"]
+
+
+class MSEEvaluator(SentenceEvaluator):
+    """sentence-transformers 2.2.2's MSEEvaluator: the mean squared error, times 100, between the teacher's embeddings of
+    `source_sentences` (taken once, here) and the evaluated model's embeddings of `target_sentences` -- the same sentences
+    for a plain distillation, their translations for a multilingual student. One forward-only qst_embed_mse call
+    (st_losses.embed_mse) on the device. Returns the negated value, so that higher is better."""
+
+    def __init__(self, source_sentences: List[str], target_sentences: List[str], teacher_model=None,
+                 show_progress_bar: bool = False, batch_size: int = 32, name: str = "", write_csv: bool = True):
+        assert len(source_sentences) == len(target_sentences)
+        self.source_embeddings = teacher_model.encode(source_sentences, show_progress_bar=show_progress_bar,
+                                                      batch_size=batch_size, convert_to_numpy=True)
+        self.target_sentences = target_sentences
+        self.show_progress_bar, self.batch_size, self.name, self.write_csv = show_progress_bar, batch_size, name, write_csv
+        self.csv_file = "mse_evaluation_" + name + "_results.csv"
+        self.csv_headers = ["epoch", "steps", "MSE"]
+
+    def mse(self, model) -> float:
+        """100 * mean((teacher - student)^2) over every element."""
+        import torch
+        from . import st_losses as S
+        target = model.encode(self.target_sentences, show_progress_bar=self.show_progress_bar, batch_size=self.batch_size,
+                              convert_to_tensor=True)
+        source = torch.as_tensor(np.asarray(self.source_embeddings, dtype=np.float32)).to(target.device)
+        with torch.no_grad():
+            return 100.0 * float(S.embed_mse(target, source).item())
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1) -> float:
+        mse = self.mse(model)
+        LOGGER.info("MSE evaluation (lower = better) on %s: MSE (*100): %.6f", self.name, mse)
+        if output_path is not None and self.write_csv:
+            _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers, [epoch, steps, mse])
+        return -mse
+
+
+def translation_matches(source_embeddings, target_embeddings):
+    """For every source row the target row with the largest cosine, and for every target row the source row: two int64
+    tensors on the device, from two util.topk_stream(k=1, mode="cos") searches -- no [N, N] matrix is built. Among equal
+    scores the smallest index wins, as np.argmax does."""
+    from . import util
+    _, s2t = util.topk_stream(source_embeddings, target_embeddings, 1, mode="cos")
+    _, t2s = util.topk_stream(target_embeddings, source_embeddings, 1, mode="cos")
+    return s2t[:, 0], t2s[:, 0]
+
+
+class TranslationEvaluator(SentenceEvaluator):
+    """sentence-transformers 2.2.2's TranslationEvaluator: source_sentences[i] and target_sentences[i] are translations of
+    each other; the accuracy of finding, by cosine similarity, sentence i of the other language among all of them, in both
+    directions (translation_matches). Returns the mean of the two accuracies."""
+
+    def __init__(self, source_sentences: List[str], target_sentences: List[str], show_progress_bar: bool = False,
+                 batch_size: int = 16, name: str = "", print_wrong_matches: bool = False, write_csv: bool = True):
+        assert len(source_sentences) == len(target_sentences)
+        self.source_sentences, self.target_sentences = source_sentences, target_sentences
+        self.show_progress_bar, self.batch_size, self.name = show_progress_bar, batch_size, name
+        self.print_wrong_matches, self.write_csv = print_wrong_matches, write_csv
+        self.csv_file = "translation_evaluation" + ("_" + name if name else "") + "_results.csv"
+        self.csv_headers = ["epoch", "steps", "src2trg", "trg2src"]
+
+    def accuracies(self, model):
+        """(src2trg, trg2src)"""
+        enc = lambda xs: model.encode(xs, show_progress_bar=self.show_progress_bar, batch_size=self.batch_size,  # noqa: E731
+                                      convert_to_tensor=True)
+        s2t, t2s = (m.cpu().numpy() for m in translation_matches(enc(self.source_sentences), enc(self.target_sentences)))
+        want = np.arange(len(self.source_sentences))
+        if self.print_wrong_matches:
+            for i in np.flatnonzero(s2t != want):
+                print("i:", int(i), "j:", int(s2t[i]), "INCORRECT")
+                print("Src:", self.source_sentences[i])
+                print("Trg:", self.target_sentences[int(s2t[i])])
+        return float(np.mean(s2t == want)), float(np.mean(t2s == want))
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1) -> float:
+        acc_src2trg, acc_trg2src = self.accuracies(model)
+        LOGGER.info("Translation evaluation on %s: src2trg %.2f trg2src %.2f", self.name, acc_src2trg * 100, acc_trg2src * 100)
+        if output_path is not None and self.write_csv:
+            _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers, [epoch, steps, acc_src2trg, acc_trg2src])
+        return (acc_src2trg + acc_trg2src) / 2
 
 
 def _unwrap_example(example):

@@ -39,9 +39,11 @@ logger = logging.getLogger(__name__)
 
 
 class InputExample:
-    """sentence_transformers.InputExample (used by models/quadruplet_sentence_transformer.py:83-97)."""
+    """sentence_transformers.InputExample (used by models/quadruplet_sentence_transformer.py:83-97). `label` is a number, or
+    a vector (numpy array, tensor or sequence of floats): the teacher's embedding that losses.MSELoss regresses on."""
 
-    def __init__(self, guid: str = "", texts: Optional[List[str]] = None, label: Union[int, float] = 0):
+    def __init__(self, guid: str = "", texts: Optional[List[str]] = None,
+                 label: Union[int, float, np.ndarray, torch.Tensor, List[float]] = 0):
         self.guid = guid
         self.texts = texts
         self.label = label
@@ -313,8 +315,7 @@ class SentenceTransformer(nn.Module):
             for idx, text in enumerate(example.texts):
                 texts[idx].append(text)
             labels.append(example.label)
-        labels = torch.tensor(labels)
-        return [self.tokenize(col) for col in texts], labels
+        return [self.tokenize(col) for col in texts], _collate_labels(labels)
 
     # ---- forward
     def forward(self, features: Dict[str, torch.Tensor], **kwargs) -> Dict[str, torch.Tensor]:
@@ -689,6 +690,20 @@ class SentenceTransformer(nn.Module):
         json.dump(modules, open(os.path.join(path, "modules.json"), "w"), indent=2)
         if self.tokenizer is not None:
             self.tokenizer.save_pretrained(path)
+
+
+def _collate_labels(labels):
+    """The labels of a batch as one tensor. Scalars go through torch.tensor as they always have. A label that is itself a
+    vector -- the teacher's embedding of the example (losses.MSELoss): a numpy array, a tensor or a sequence -- is stacked
+    to [B, D] fp32; tensors that live on a device are stacked there and stay there."""
+    first = labels[0] if labels else None
+    if isinstance(first, torch.Tensor) and first.dim() > 0:
+        return torch.stack([torch.as_tensor(v) for v in labels]).to(torch.float32)
+    if isinstance(first, np.ndarray) and first.ndim > 0:
+        return torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32) for v in labels]))
+    if isinstance(first, (list, tuple)):
+        return torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32) for v in labels]))
+    return torch.tensor(labels)
 
 
 def _shard_batch(features, labels, rank: int, world: int):

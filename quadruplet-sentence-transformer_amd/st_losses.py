@@ -32,6 +32,14 @@ step: distance matrix, mining, loss and the gradient through the selections are 
 `f(embeddings) -> [B, B]` and the mining runs in torch on its result -- `eucledian_distance` with `squared=True` goes that
 way. `data.SentenceLabelDataset` is the loader they are meant to be fed by. Under `split_batch` rank r mines among rows
 r::world of the batch only, so `samples_per_label` must be at least 2 * world for a rank to see a positive.
+
+`MSELoss` and `MarginMSELoss` distil from a teacher (csrc/distill.hip). `MSELoss` takes ONE text column and the teacher's
+embedding of each example as its label ([B, D]: SentenceTransformer.smart_batching_collate stacks vector labels, and
+`data.ParallelSentencesDataset` produces them); value and gradient are one qst_embed_mse call. `MarginMSELoss` takes
+(query, positive, negative) and the teacher's score margin per example; with `util.pairwise_dot_score` (the default) or
+`util.pairwise_cos_sim` -- recognised by identity, like the similarity functions above -- the two similarities, their
+difference, the squared error and all three gradients are one qst_margin_mse_loss call; any other callable
+`f(a, b) -> [B]` is called on the embeddings and the rest runs in torch.
 """
 from __future__ import annotations
 
@@ -136,6 +144,38 @@ def batch_triplet_loss_raw(x, labels, kind: int, metric: int, margin: float, gra
     return out, grad, counts
 
 
+def embed_mse_raw(x, t, grad_out: Optional[torch.Tensor] = None, want_grads: bool = False):
+    """qst_embed_mse on contiguous fp32 HIP tensors [B, D]: mean((x - t)^2) [1] and, with want_grads, the gradient in x
+    times grad_out (a device scalar; None = 1), else None."""
+    lib = _lib.load()
+    B, D = x.shape
+    out = torch.empty(1, dtype=torch.float32, device=x.device)
+    scratch = torch.empty(B, dtype=torch.float32, device=x.device)
+    grad = torch.empty_like(x) if want_grads else None
+    with torch.cuda.device(x.device):
+        _lib.check(lib.qst_embed_mse(x.data_ptr(), t.data_ptr(), B, D, out.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grad),
+                                     scratch.data_ptr(), _lib.current_stream_ptr()), "qst_embed_mse")
+    return out, grad
+
+
+def margin_mse_raw(q, p, n, labels, sim: int, reduction: int, grad_out: Optional[torch.Tensor] = None,
+                   want_grads: bool = False, want_margin: bool = False):
+    """qst_margin_mse_loss: (sim(q, p) - sim(q, n) - labels)^2 per row or reduced (sim METRIC_DOT or METRIC_COS_SIM), the
+    three gradients, and with want_margin the margins [B] as a third result."""
+    lib = _lib.load()
+    B, D = q.shape
+    out = torch.empty(B if reduction == 0 else 1, dtype=torch.float32, device=q.device)
+    scratch = torch.empty(B, dtype=torch.float32, device=q.device)
+    margin = torch.empty(B, dtype=torch.float32, device=q.device) if want_margin else None
+    grads = _grad_slabs(3, q, want_grads)
+    with torch.cuda.device(q.device):
+        _lib.check(lib.qst_margin_mse_loss(q.data_ptr(), p.data_ptr(), n.data_ptr(), labels.data_ptr(), B, D, int(sim),
+                                           int(reduction), out.data_ptr(), _lib.ptr(margin), _lib.ptr(grad_out),
+                                           *[_lib.ptr(g) for g in grads], scratch.data_ptr(), _lib.current_stream_ptr()),
+                   "qst_margin_mse_loss")
+    return (out, grads, margin) if want_margin else (out, grads)
+
+
 # ------------------------------------------------------------------ autograd (save the inputs, recompute in backward)
 def _f32(xs):
     return [x.detach().to(torch.float32).contiguous() for x in xs]
@@ -225,6 +265,37 @@ class _BatchTripletFn(torch.autograd.Function):
         return grad.to(ctx.in_dtype), None, None, None, None
 
 
+class _EmbedMseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t):
+        xs = _f32((x, t))
+        out, _ = embed_mse_raw(*xs)
+        ctx.save_for_backward(*xs)
+        ctx.in_dtype = x.dtype
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        _, grad = embed_mse_raw(*ctx.saved_tensors, grad_out=_upstream(grad_output), want_grads=True)
+        return grad.to(ctx.in_dtype), None
+
+
+class _MarginMseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, p, n, labels, sim, red_code):
+        xs = _f32((q, p, n))
+        y = labels.detach().to(torch.float32).contiguous().reshape(-1)
+        out, _ = margin_mse_raw(*xs, y, sim, red_code)
+        ctx.save_for_backward(*xs, y)
+        ctx.hp, ctx.in_dtypes = (sim, red_code), (q.dtype, p.dtype, n.dtype)
+        return out if red_code == 0 else out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        _, grads = margin_mse_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
+        return (*[g.to(dt) for g, dt in zip(grads, ctx.in_dtypes)], None, None, None)
+
+
 def _require_rows(what: str, *xs) -> None:
     if any(x.dim() != 2 for x in xs) or any(x.shape != xs[0].shape for x in xs):
         raise ValueError(f"{what}: the embeddings must all have the same shape (B, D)")
@@ -302,6 +373,27 @@ def batch_triplet_loss(x: torch.Tensor, labels: torch.Tensor, kind: int = BT_HAR
     _require_rows("batch_triplet_loss", x)
     _require_labels("batch_triplet_loss", labels, x.shape[0])
     return _BatchTripletFn.apply(x, labels, int(kind), int(metric), float(margin))
+
+
+def embed_mse(x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """torch.nn.MSELoss()(x, t) of two [B, D] HIP tensors: the mean over all B * D elements of (x - t)^2. One qst_embed_mse
+    call, differentiable in x; the target carries no gradient."""
+    if x.dim() != 2 or x.shape != t.shape or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"embed_mse: embeddings {tuple(x.shape)} and targets {tuple(t.shape)} must share one shape (B, D)")
+    _require_rows("embed_mse", x, t)
+    return _EmbedMseFn.apply(x, t)
+
+
+def margin_mse(q, p, n, labels, sim: int = METRIC_DOT, reduction: str = "mean") -> torch.Tensor:
+    """(sim(q, p) - sim(q, n) - labels)^2 of three [B, D] HIP tensors and the teacher's margins [B], sim METRIC_DOT or
+    METRIC_COS_SIM. One qst_margin_mse_loss call, differentiable in q, p and n."""
+    if sim not in (METRIC_DOT, METRIC_COS_SIM):
+        raise ValueError(f"sim is METRIC_DOT or METRIC_COS_SIM, {sim!r} given")
+    if q.dim() == 2 and labels.numel() != q.shape[0]:
+        raise ValueError(f"margin_mse: {q.shape[0]} rows but {labels.numel()} labels")
+    _require_rows("margin_mse", q, p, n)
+    _require_labels("margin_mse", labels, q.shape[0])
+    return _MarginMseFn.apply(q, p, n, labels, int(sim), _RED_CODE[reduction])
 
 
 def quadruplet_eval_raw(a, p, q, n, want_dist: bool = False):
@@ -656,3 +748,49 @@ class BatchAllTripletLoss(_BatchTripletLoss):
 
     def batch_all_triplet_loss(self, labels: torch.Tensor, embeddings: torch.Tensor) -> torch.Tensor:
         return self._loss(labels, embeddings)
+
+
+# ------------------------------------------------------------------ distillation from a teacher
+class MSELoss(_TupleLoss):
+    """nn.MSELoss() between the student's embedding of the one text column and `labels`, the teacher's embedding of each
+    example [B, D]: one qst_embed_mse call. The teacher and the student must have the same embedding width (sentence-
+    transformers users put a Dense or PCA layer in between otherwise; that is not done here)."""
+    reduction = "mean"
+
+    def __init__(self, model):
+        super().__init__(model, True)
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor) -> torch.Tensor:
+        cols = list(sentence_features)
+        rep = self.model(cols[0])["sentence_embedding"]
+        if labels.dim() != 2 or labels.shape != rep.shape:
+            raise ValueError(f"MSELoss: the labels are the teacher's embeddings, shape {tuple(rep.shape)} like the student's; "
+                             f"{tuple(labels.shape)} given")
+        return embed_mse(rep, labels)
+
+
+class MarginMSELoss(_TupleLoss):
+    """mean over the batch of (similarity_fct(query, positive) - similarity_fct(query, negative) - label)^2, the label
+    being the teacher's (usually a cross-encoder's) margin score(query, positive) - score(query, negative). With
+    `util.pairwise_dot_score` or `util.pairwise_cos_sim` one qst_margin_mse_loss call; any other callable
+    `f(a, b) -> [B]` is called on the embeddings as given and the squared error runs in torch."""
+    reduction = "mean"
+
+    def __init__(self, model, similarity_fct=util.pairwise_dot_score, fused: bool = True):
+        super().__init__(model, fused)
+        self.similarity_fct = similarity_fct
+
+    def _kernel_sim(self) -> Optional[int]:
+        if self.similarity_fct is util.pairwise_dot_score:
+            return METRIC_DOT
+        if self.similarity_fct is util.pairwise_cos_sim:
+            return METRIC_COS_SIM
+        return None
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor) -> torch.Tensor:
+        q, p, n = self._embed(sentence_features, 3)
+        sim = self._kernel_sim()
+        if sim is not None:
+            return margin_mse(q, p, n, labels.view(-1), sim, "mean")
+        margin = self.similarity_fct(q, p) - self.similarity_fct(q, n)
+        return torch.nn.functional.mse_loss(margin, labels.view(-1).to(margin.dtype))

@@ -87,6 +87,21 @@ def euclidean_score(a, b) -> torch.Tensor:
     return score_matrix(a, b, SCORE_EUCLID)
 
 
+def pairwise_dot_score(a, b) -> torch.Tensor:
+    """sentence_transformers.util.pairwise_dot_score: the dot product of row i of `a` with row i of `b`, [B]
+    (qst_pair_metric with its autograd; HIP tensors only)."""
+    from . import st_losses
+    return st_losses.pair_metric(a, b, st_losses.METRIC_DOT)
+
+
+def pairwise_cos_sim(a, b) -> torch.Tensor:
+    """sentence_transformers.util.pairwise_cos_sim: the cosine of row i of `a` and row i of `b`, [B] (qst_pair_metric with
+    its autograd; HIP tensors only). Each norm is clamped at 1e-8 as in F.cosine_similarity; 2.2.2 normalises the rows with
+    eps 1e-12 first, which differs only for rows with a norm below 1e-8."""
+    from . import st_losses
+    return st_losses.pair_metric(a, b, st_losses.METRIC_COS_SIM)
+
+
 # marks this package's own score functions: evaluators route them (and callables that behave like them) to the fused
 # score + top-k kernel instead of materialising the matrix
 cos_sim._qst_mode = SCORE_COS
