@@ -8,49 +8,11 @@
 // D = 2048 (past that the gradient pass re-reads them, still 16 bytes a lane), reduces with DPP, and writes the gradients from
 // the registers. The per-row values go through a one-workgroup second stage that sums in double, in a fixed order: B can be
 // a whole evaluation set, and the squared error of every row has the same sign. No atomics anywhere: the same inputs give
-// the same bits. HBM-bound: 2 (3) rows read and, with gradients, 1 (3) written.
-#include "qst_common.h"
+// the same bits. HBM-bound: 2 (3) rows read and, with gradients, 1 (3) written. The choice of the form, the second stage and
+// the cosine's scalars are row_loss.h's, shared with loss.hip and tuple_loss.hip.
+#include "row_loss.h"
 
 namespace {
-
-constexpr float kCosEps = 1e-8f;    // torch cosine_similarity default eps (each norm clamped on its own), as qst_pair_metric
-constexpr int kMaxVec = 8;          // float4 per lane and row kept in registers -> D <= 64*4*8 = 2048
-
-// wave_sum (qst_common.h) on a double: the same tree, each half of the value moved by its own DPP / readlane
-template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double v) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xf, 0xf, true);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double lane_bcast_f64(double v, int lane) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    v += dpp_mov_f64<0xB1>(v);
-    v += dpp_mov_f64<0x4E>(v);
-    v += dpp_mov_f64<0x141>(v);
-    v += dpp_mov_f64<0x140>(v);
-    return (lane_bcast_f64(v, 0) + lane_bcast_f64(v, 16)) + (lane_bcast_f64(v, 32) + lane_bcast_f64(v, 48));
-}
-
-// ---- second stage: one workgroup over the per-row values, summed in double. Thread i takes rows i, i + 1024, ... in that
-// order, then the wave tree, then the 16 wave totals through the same tree: a fixed order. div = 1 (sum), B (mean over the
-// rows) or B * D (mean over the elements), divided in double and rounded to fp32 once.
-__global__ __launch_bounds__(1024) void distill_reduce_kernel(const float* rows, int B, double div, float* out) {
-    __shared__ double part[16];
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < B; i += 1024) s += (double)rows[i];   // 64-bit: i passes B, and B may be near INT_MAX
-    s = wave_sum_f64(s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    double r = (threadIdx.x & 63) < 16 ? part[threadIdx.x & 63] : 0.0;
-    r = wave_sum_f64(r);
-    if (threadIdx.x == 0) out[0] = (float)(r / div);
-}
 
 // ---- qst_embed_mse
 struct MseArgs {
@@ -69,10 +31,10 @@ template <int NV, bool VEC>
 __global__ __launch_bounds__(256) void embed_mse_kernel(MseArgs a) {
     constexpr int kVec = NV > 0 ? NV : 1;
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= a.B) return;
+    int64_t row;
+    if (!wave_row(a.B, row)) return;
     const int D = a.D;
-    const size_t base = (size_t)row * D;
+    const size_t base = row_base(row, D);
     const float* x = a.x + base;
     const float* t = a.t + base;
     const int nv = D >> 2;
@@ -153,30 +115,19 @@ __device__ __forceinline__ void margin_accum(float q, float p, float n, float (&
 
 // sim(q, y) and the scalars of its gradient: d sim / dq = kxy * y + kxx * q, d sim / dy = kxy * q + kyy * y -- the formulas
 // of qst_pair_metric (tuple_loss.hip): a norm at or below the clamp is a constant and passes no gradient
-struct SimVal { float m, kxy, kxx, kyy; };
 template <bool COS>
-__device__ __forceinline__ SimVal sim_finish(float dot, float nx, float ny) {
-    SimVal r = {dot, 1.f, 0.f, 0.f};
-    if (COS) {
-        const float cx = fmaxf(nx, kCosEps), cy = fmaxf(ny, kCosEps);
-        const float inv = 1.f / (cx * cy);
-        const float cs = dot * inv;
-        r.m = cs;
-        r.kxy = inv;
-        r.kxx = nx > kCosEps ? -cs / (cx * cx) : 0.f;
-        r.kyy = ny > kCosEps ? -cs / (cy * cy) : 0.f;
-    }
-    return r;
+__device__ __forceinline__ CosVal sim_finish(float dot, float nx, float ny) {
+    return COS ? cos_finish(dot, nx, ny, false) : CosVal{dot, 1.f, 0.f, 0.f};
 }
 
 template <bool COS, int NV, bool VEC>
 __global__ __launch_bounds__(256) void margin_mse_kernel(MarginArgs a) {
     constexpr int kVec = NV > 0 ? NV : 1;
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= a.B) return;
+    int64_t row;
+    if (!wave_row(a.B, row)) return;
     const int D = a.D;
-    const size_t base = (size_t)row * D;
+    const size_t base = row_base(row, D);
     const float* xq = a.x[0] + base;
     const float* xp = a.x[1] + base;
     const float* xn = a.x[2] + base;
@@ -208,7 +159,7 @@ __global__ __launch_bounds__(256) void margin_mse_kernel(MarginArgs a) {
     const float dqp = wave_sum(s[0]), dqn = wave_sum(s[1]);
     float nq = 0.f, np = 0.f, nn = 0.f;
     if (COS) { nq = sqrtf(wave_sum(s[2])); np = sqrtf(wave_sum(s[3])); nn = sqrtf(wave_sum(s[4])); }
-    const SimVal sp = sim_finish<COS>(dqp, nq, np), sn = sim_finish<COS>(dqn, nq, nn);
+    const CosVal sp = sim_finish<COS>(dqp, nq, np), sn = sim_finish<COS>(dqn, nq, nn);
 
     const float m = sp.m - sn.m;
     const float e = m - a.labels[row];
@@ -268,52 +219,18 @@ __global__ __launch_bounds__(256) void margin_mse_kernel(MarginArgs a) {
     }
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// which of the three forms a launch takes: NV of the register-resident form (0 = a streaming form) and whether the
-// streaming form loads 16 bytes a lane
-void pick_form(int D, bool aligned, int& nvreg, bool& vec) {
-    vec = (D % 4 == 0) && aligned;
-    nvreg = 0;
-    if (vec && D <= 64 * 4 * kMaxVec) {
-        const int n = (D + 255) / 256;
-        nvreg = n <= 4 ? n : kMaxVec;
-    }
-}
-
 void launch_mse(const MseArgs& a, hipStream_t st) {
-    int nvreg; bool vec;
-    pick_form(a.D, al16(a.x) && al16(a.t) && (!a.g || al16(a.g)), nvreg, vec);
-    const int grid = (int)(((int64_t)a.B + 3) / 4);
-    switch (nvreg) {
-        case 1: embed_mse_kernel<1, true><<<grid, 256, 0, st>>>(a); break;
-        case 2: embed_mse_kernel<2, true><<<grid, 256, 0, st>>>(a); break;
-        case 3: embed_mse_kernel<3, true><<<grid, 256, 0, st>>>(a); break;
-        case 4: embed_mse_kernel<4, true><<<grid, 256, 0, st>>>(a); break;
-        case 8: embed_mse_kernel<8, true><<<grid, 256, 0, st>>>(a); break;
-        default:
-            if (vec) embed_mse_kernel<0, true><<<grid, 256, 0, st>>>(a);
-            else embed_mse_kernel<0, false><<<grid, 256, 0, st>>>(a);
-    }
+    const float* x[2] = {a.x, a.t};
+    dispatch_form<true>(a.D, rows_al16(x, 2, &a.g, 1), [&](auto nv, auto vec) {
+        embed_mse_kernel<decltype(nv)::value, decltype(vec)::value><<<row_grid(a.B), 256, 0, st>>>(a);
+    });
 }
 
 template <bool COS>
 void launch_margin(const MarginArgs& a, hipStream_t st) {
-    bool aligned = true;
-    for (int k = 0; k < 3; ++k) aligned = aligned && al16(a.x[k]) && (!a.g[0] || al16(a.g[k]));
-    int nvreg; bool vec;
-    pick_form(a.D, aligned, nvreg, vec);
-    const int grid = (int)(((int64_t)a.B + 3) / 4);
-    switch (nvreg) {
-        case 1: margin_mse_kernel<COS, 1, true><<<grid, 256, 0, st>>>(a); break;
-        case 2: margin_mse_kernel<COS, 2, true><<<grid, 256, 0, st>>>(a); break;
-        case 3: margin_mse_kernel<COS, 3, true><<<grid, 256, 0, st>>>(a); break;
-        case 4: margin_mse_kernel<COS, 4, true><<<grid, 256, 0, st>>>(a); break;
-        case 8: margin_mse_kernel<COS, 8, true><<<grid, 256, 0, st>>>(a); break;
-        default:
-            if (vec) margin_mse_kernel<COS, 0, true><<<grid, 256, 0, st>>>(a);
-            else margin_mse_kernel<COS, 0, false><<<grid, 256, 0, st>>>(a);
-    }
+    dispatch_form<true>(a.D, rows_al16(a.x, 3, a.g, 3), [&](auto nv, auto vec) {
+        margin_mse_kernel<COS, decltype(nv)::value, decltype(vec)::value><<<row_grid(a.B), 256, 0, st>>>(a);
+    });
 }
 
 }  // namespace
@@ -328,7 +245,7 @@ extern "C" int qst_embed_mse(const float* x, const float* t, int B, int D, float
     a.k = (float)(2.0 / ((double)B * (double)D));
     launch_mse(a, st);
     QST_LAUNCH_CHECK();
-    distill_reduce_kernel<<<1, 1024, 0, st>>>(scratch, B, (double)B * (double)D, out_loss);
+    row_sum_kernel<double><<<1, 1024, 0, st>>>(scratch, B, (double)B * (double)D, out_loss);
     QST_LAUNCH_CHECK();
     return QST_OK;
 }
@@ -353,7 +270,7 @@ extern "C" int qst_margin_mse_loss(const float* q, const float* p, const float* 
     else launch_margin<false>(a, st);
     QST_LAUNCH_CHECK();
     if (reduction != QST_REDUCE_NONE) {
-        distill_reduce_kernel<<<1, 1024, 0, st>>>(scratch, B, reduction == QST_REDUCE_MEAN ? (double)B : 1.0, out_loss);
+        row_sum_kernel<double><<<1, 1024, 0, st>>>(scratch, B, reduction == QST_REDUCE_MEAN ? (double)B : 1.0, out_loss);
         QST_LAUNCH_CHECK();
     }
     return QST_OK;

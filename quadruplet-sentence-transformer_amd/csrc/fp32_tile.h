@@ -9,7 +9,6 @@ constexpr int kBK = 16;                 // K panel
 constexpr int kLdT = kTile + 4;         // LDS row pitch in floats (16-byte multiple)
 
 inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
-inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 // ---- fixed-order block reductions over `NW` waves
 template <int NW>

@@ -6,13 +6,13 @@
 //   TML(x,y,z;m) = max(m + ||x-y+eps||_p - dneg, 0),  dneg = ||x-z+eps||_p, swap: min(dneg, ||y-z+eps||_p)
 //   row = a + gamma*b + (1-gamma)*c
 // HBM-bound: algorithmic bytes = 4*D*4 read per row (+ 4*D*4 written with gradients). The four
-// rows are read once with 16-byte coalesced loads and kept in registers for the gradient pass.
-#include "qst_common.h"
+// rows are read once with 16-byte coalesced loads and kept in registers for the gradient pass. The choice of the form and
+// the second stage are row_loss.h's, shared with tuple_loss.hip and distill.hip.
+#include "row_loss.h"
 
 namespace {
 
 constexpr float kEps = 1e-6f;       // torch pairwise_distance default eps
-constexpr int kMaxVecAll = 8;       // float4 per lane kept in registers -> D <= 64*4*8 = 2048
 
 struct LossArgs {
     const float* x[4];              // A, P, Q, N
@@ -58,10 +58,10 @@ __global__ __launch_bounds__(256) void quad_loss_kernel(LossArgs a) {
     constexpr bool VEC = NV > 0;
     constexpr int kMaxVec = NV > 0 ? NV : 1;
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= a.B) return;
+    int64_t row;
+    if (!wave_row(a.B, row)) return;
     const int D = a.D;
-    const size_t base = (size_t)row * D;
+    const size_t base = row_base(row, D);
 
     float xa[VEC ? kMaxVec * 4 : 1], xp[VEC ? kMaxVec * 4 : 1], xq[VEC ? kMaxVec * 4 : 1], xn[VEC ? kMaxVec * 4 : 1];
     float s[6] = {0, 0, 0, 0, 0, 0};
@@ -196,31 +196,11 @@ __global__ __launch_bounds__(256) void quad_loss_kernel(LossArgs a) {
     }
 }
 
-// Deterministic second stage for 'sum'/'mean': one block, fixed summation tree.
-__global__ __launch_bounds__(1024) void quad_loss_reduce_kernel(const float* rows, int B, float scale, float* out) {
-    __shared__ float part[16];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < B; i += 1024) s += rows[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float v = threadIdx.x < 16 ? part[threadIdx.x] : 0.f;
-        v = wave_sum(v);
-        if (threadIdx.x == 0) out[0] = v * scale;
-    }
-}
-
 template <int PMODE>
-void launch_loss(const LossArgs& a, bool vec, hipStream_t st) {
-    const int grid = (a.B + 3) / 4;
-    const int nv = (a.D + 255) / 256;
-    if (!vec) quad_loss_kernel<PMODE, 0><<<grid, 256, 0, st>>>(a);
-    else if (nv <= 1) quad_loss_kernel<PMODE, 1><<<grid, 256, 0, st>>>(a);
-    else if (nv <= 2) quad_loss_kernel<PMODE, 2><<<grid, 256, 0, st>>>(a);
-    else if (nv <= 3) quad_loss_kernel<PMODE, 3><<<grid, 256, 0, st>>>(a);
-    else if (nv <= 4) quad_loss_kernel<PMODE, 4><<<grid, 256, 0, st>>>(a);
-    else quad_loss_kernel<PMODE, 8><<<grid, 256, 0, st>>>(a);
+void launch_loss(const LossArgs& a, hipStream_t st) {
+    dispatch_form<false>(a.D, rows_al16(a.x, 4, a.g, 4), [&](auto nv, auto) {
+        quad_loss_kernel<PMODE, decltype(nv)::value><<<row_grid(a.B), 256, 0, st>>>(a);
+    });
 }
 
 }  // namespace
@@ -248,16 +228,13 @@ extern "C" int qst_quadruplet_loss(const float* xa, const float* xp, const float
     a.row_out = (reduction == QST_REDUCE_NONE) ? out_loss : scratch;
     a.B = B; a.D = D; a.gamma = gamma; a.m_pn = margin_pos_neg; a.m_pq = margin_pos_part; a.m_qn = margin_part_neg;
     a.p = p; a.swap = swap; a.reduction = reduction;
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    bool vec = (D % 4 == 0) && D <= 64 * 4 * kMaxVecAll && al16(xa) && al16(xp) && al16(xq) && al16(xn);
-    if (any_g) vec = vec && al16(grad_a) && al16(grad_p) && al16(grad_q) && al16(grad_n);
-    if (p == 2.0f) launch_loss<2>(a, vec, st);
-    else if (p == 1.0f) launch_loss<1>(a, vec, st);
-    else launch_loss<0>(a, vec, st);
+    if (p == 2.0f) launch_loss<2>(a, st);
+    else if (p == 1.0f) launch_loss<1>(a, st);
+    else launch_loss<0>(a, st);
     QST_LAUNCH_CHECK();
     if (reduction != QST_REDUCE_NONE) {
         const float scale = (reduction == QST_REDUCE_MEAN) ? 1.0f / (float)B : 1.0f;
-        quad_loss_reduce_kernel<<<1, 1024, 0, st>>>(scratch, B, scale, out_loss);
+        row_sum_kernel<float><<<1, 1024, 0, st>>>(scratch, B, scale, out_loss);
         QST_LAUNCH_CHECK();
     }
     return QST_OK;

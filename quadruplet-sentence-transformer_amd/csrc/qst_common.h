@@ -128,6 +128,26 @@ __device__ __forceinline__ float wave_max(float v) {
     v = row16_max(v);
     return fmaxf(fmaxf(lane_bcast(v, 0), lane_bcast(v, 16)), fmaxf(lane_bcast(v, 32), lane_bcast(v, 48)));
 }
+// wave_sum on a double: the same tree, each half of the value moved by its own DPP / readlane
+template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double v) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xf, 0xf, true);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double lane_bcast_f64(double v, int lane) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    v += dpp_mov_f64<0xB1>(v);
+    v += dpp_mov_f64<0x4E>(v);
+    v += dpp_mov_f64<0x141>(v);
+    v += dpp_mov_f64<0x140>(v);
+    return (lane_bcast_f64(v, 0) + lane_bcast_f64(v, 16)) + (lane_bcast_f64(v, 32) + lane_bcast_f64(v, 48));
+}
 // exchange with the lane 32 away (the other half of an MFMA 32x32 accumulator column)
 __device__ __forceinline__ float swap32(float v) {
     // v_permlane32_swap: lanes 32-63 of the first operand trade places with lanes 0-31 of the second (VALU, no LDS)
@@ -284,6 +304,7 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 }
 
 static inline int64_t qst_align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+static inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }    // may be read or written 16 bytes a lane
 
 // ---------------------------------------------------------------- dropout masks (include/qst_kernels.h: QstDrop)
 __device__ __forceinline__ uint32_t qst_hash32(uint32_t x) {

@@ -4,7 +4,8 @@
 // CosineSimilarityLoss, ContrastiveLoss, OnlineContrastiveLoss, TripletLoss, and the per-row metric itself (what
 // EmbeddingSimilarityEvaluator scores with). Each is a function of one or two pair metrics per row, so every kernel here has
 // quad_loss_kernel's shape: the rows are read once with 16-byte coalesced loads, kept in registers, reduced with DPP, and the
-// gradient pass runs from the registers. HBM-bound: k*D*4 bytes read per row (+ as many written with gradients).
+// gradient pass runs from the registers. HBM-bound: k*D*4 bytes read per row (+ as many written with gradients). The choice of
+// the form, the sum over the rows and the cosine's scalars are row_loss.h's, shared with loss.hip and distill.hip.
 //
 //   COS_SIM  u.v / (max(|u|, 1e-8) max(|v|, 1e-8))     COS_DIST 1 - COS_SIM     DOT u.v
 //   L2 / L1  |u - v + 1e-6|_p (torch pairwise_distance) L2_PLAIN / L1_PLAIN |u - v|_p
@@ -14,13 +15,11 @@
 // gradient, and among a few thousand rows some always lie that close. The L1 hinges take d as a double; what is stored and
 // returned stays fp32. L2 (sqrt(2 D) for random rows, 0.3 of the gradient tolerance on the same rows) and the cosine metrics
 // (bounded by 2) stay in fp32, bit for bit as before. The kernels stay HBM-bound.
-#include "qst_common.h"
+#include "row_loss.h"
 
 namespace {
 
 constexpr float kPairEps = 1e-6f;   // torch pairwise_distance default eps (added to the difference)
-constexpr float kCosEps = 1e-8f;    // torch cosine_similarity default eps (each norm clamped on its own)
-constexpr int kMaxVecAll = 8;       // float4 per lane kept in registers -> D <= 64*4*8 = 2048
 
 enum { MODE_METRIC = 0, MODE_MSE, MODE_CONTRASTIVE, MODE_ONLINE_FWD, MODE_ONLINE_BWD, MODE_TRIPLET };
 
@@ -34,27 +33,6 @@ struct TupleArgs {
     int B, D, mode, metric, reduction;
     float margin, eps;
 };
-
-// wave_sum (qst_common.h) on a double: the same tree, each half of the value moved by its own DPP / readlane
-template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double v) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xf, 0xf, true);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double lane_bcast_f64(double v, int lane) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    v += dpp_mov_f64<0xB1>(v);
-    v += dpp_mov_f64<0x4E>(v);
-    v += dpp_mov_f64<0x141>(v);
-    v += dpp_mov_f64<0x140>(v);
-    return (lane_bcast_f64(v, 0) + lane_bcast_f64(v, 16)) + (lane_bcast_f64(v, 32) + lane_bcast_f64(v, 48));
-}
 
 // metric class: 0 = products (cosine, dot), 1 = L2 of the difference, 2 = L1 of the difference (summed in fp64 into sd)
 // EXACT: every product-and-add is an explicit fma, so the compiler has no choice between fused and unfused forms (left to
@@ -87,9 +65,9 @@ __device__ __forceinline__ PairVal finish(const float (&s)[3], double sd, int me
         const float dot = wave_sum(s[0]);
         if (metric == QST_METRIC_DOT) { r.m = dot; r.kxy = 1.f; r.md = (double)dot; return r; }
         const float nx = sqrtf(wave_sum(s[1])), ny = sqrtf(wave_sum(s[2]));
-        const float cx = fmaxf(nx, kCosEps), cy = fmaxf(ny, kCosEps);
         if (EXACT) {
 #pragma clang fp contract(off)
+            const float cx = fmaxf(nx, kCosEps), cy = fmaxf(ny, kCosEps);
             const float den = cx * cy;
             const float inv = 1.f / den;
             const float cs = dot * inv;
@@ -97,13 +75,8 @@ __device__ __forceinline__ PairVal finish(const float (&s)[3], double sd, int me
             r.md = (double)r.m;
             return r;
         }
-        const float inv = 1.f / (cx * cy);
-        const float cs = dot * inv;
-        const float sg = (metric == QST_METRIC_COS_DIST) ? -1.f : 1.f;
-        r.m = (metric == QST_METRIC_COS_DIST) ? 1.f - cs : cs;
-        r.kxy = sg * inv;
-        r.kxx = nx > kCosEps ? -sg * cs / (cx * cx) : 0.f;      // a clamped norm is a constant
-        r.kyy = ny > kCosEps ? -sg * cs / (cy * cy) : 0.f;
+        const CosVal c = cos_finish(dot, nx, ny, metric == QST_METRIC_COS_DIST);
+        r.m = c.m; r.kxy = c.kxy; r.kxx = c.kxx; r.kyy = c.kyy;
         r.md = (double)r.m;
     } else if (MC == 1) {
         r.m = sqrtf(wave_sum(s[0]));
@@ -138,10 +111,10 @@ __global__ __launch_bounds__(256) void tuple_loss_kernel(TupleArgs a) {
     constexpr int kVec = NV > 0 ? NV : 1;
     constexpr int NP = NX - 1;                      // pairs: (x0, x1)[, (x0, x2)]
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= a.B) return;
+    int64_t row;
+    if (!wave_row(a.B, row)) return;
     const int D = a.D;
-    const size_t base = (size_t)row * D;
+    const size_t base = row_base(row, D);
     const float eps = a.eps;
 
     float xr[NX][VEC ? kVec * 4 : 1];
@@ -277,14 +250,6 @@ __device__ __forceinline__ float block_reduce(float v, float* part) {
     return r;
 }
 
-__global__ __launch_bounds__(1024) void tuple_reduce_kernel(const float* rows, int B, float scale, float* out) {
-    __shared__ float part[16];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < B; i += 1024) s += rows[i];
-    s = block_reduce<OP_SUM>(s, part);
-    if (threadIdx.x == 0) out[0] = s * scale;
-}
-
 // OnlineContrastiveLoss's selection: the thresholds from the other class, then the sum over the selected rows.
 // d: distances [B] followed by the two thresholds this kernel writes for the gradient launch.
 __global__ __launch_bounds__(1024) void online_select_kernel(float* d, const float* labels, int B, float margin, float* out) {
@@ -311,29 +276,18 @@ __global__ __launch_bounds__(1024) void online_select_kernel(float* d, const flo
     if (threadIdx.x == 0) { d[B] = t_pos; d[B + 1] = t_neg; out[0] = s; }
 }
 
-template <int MC, int NX>
-void launch_nv(const TupleArgs& a, bool vec, hipStream_t st) {
-    const int grid = (a.B + 3) / 4;
-    const int nv = (a.D + 255) / 256;
-    if (!vec) tuple_loss_kernel<MC, NX, 0><<<grid, 256, 0, st>>>(a);
-    else if (nv <= 1) tuple_loss_kernel<MC, NX, 1><<<grid, 256, 0, st>>>(a);
-    else if (nv <= 2) tuple_loss_kernel<MC, NX, 2><<<grid, 256, 0, st>>>(a);
-    else if (nv <= 3) tuple_loss_kernel<MC, NX, 3><<<grid, 256, 0, st>>>(a);
-    else if (nv <= 4) tuple_loss_kernel<MC, NX, 4><<<grid, 256, 0, st>>>(a);
-    else tuple_loss_kernel<MC, NX, 8><<<grid, 256, 0, st>>>(a);
-}
-
 template <int NX>
 void launch_rows(TupleArgs a, hipStream_t st) {
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    bool vec = (a.D % 4 == 0) && a.D <= 64 * 4 * kMaxVecAll;
-    for (int k = 0; k < NX; ++k) vec = vec && al16(a.x[k]) && (!a.g[0] || al16(a.g[k]));
     a.eps = (a.metric == QST_METRIC_L2 || a.metric == QST_METRIC_L1) ? kPairEps : 0.f;
-    switch (a.metric) {
-        case QST_METRIC_L2: case QST_METRIC_L2_PLAIN: launch_nv<1, NX>(a, vec, st); break;
-        case QST_METRIC_L1: case QST_METRIC_L1_PLAIN: launch_nv<2, NX>(a, vec, st); break;
-        default: launch_nv<0, NX>(a, vec, st); break;
-    }
+    dispatch_form<false>(a.D, rows_al16(a.x, NX, a.g, NX), [&](auto nv, auto) {
+        constexpr int NV = decltype(nv)::value;
+        const int grid = row_grid(a.B);
+        switch (a.metric) {
+            case QST_METRIC_L2: case QST_METRIC_L2_PLAIN: tuple_loss_kernel<1, NX, NV><<<grid, 256, 0, st>>>(a); break;
+            case QST_METRIC_L1: case QST_METRIC_L1_PLAIN: tuple_loss_kernel<2, NX, NV><<<grid, 256, 0, st>>>(a); break;
+            default: tuple_loss_kernel<0, NX, NV><<<grid, 256, 0, st>>>(a); break;
+        }
+    });
 }
 
 bool grads_ok(float* const* g, int n, bool& any) {
@@ -378,10 +332,10 @@ __device__ __forceinline__ void quad_accum(QuadAcc& q, float x0, float x1, float
 template <bool VEC>
 __global__ __launch_bounds__(256) void quad_eval_kernel(QuadEvalArgs a) {
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= a.B) return;
+    int64_t row;
+    if (!wave_row(a.B, row)) return;
     const int D = a.D;
-    const size_t base = (size_t)row * D;
+    const size_t base = row_base(row, D);
     const float* xa = a.x[0] + base;
     const float* xp = a.x[1] + base;
     const float* xq = a.x[2] + base;
@@ -513,7 +467,7 @@ extern "C" int qst_pair_loss(const float* u, const float* v, const float* labels
     launch_rows<2>(a, st);
     QST_LAUNCH_CHECK();
     if (reduction != QST_REDUCE_NONE) {
-        tuple_reduce_kernel<<<1, 1024, 0, st>>>(scratch, B, reduction == QST_REDUCE_MEAN ? 1.0f / (float)B : 1.0f, out_loss);
+        row_sum_kernel<float><<<1, 1024, 0, st>>>(scratch, B, reduction == QST_REDUCE_MEAN ? 1.0f / (float)B : 1.0f, out_loss);
         QST_LAUNCH_CHECK();
     }
     return QST_OK;
@@ -539,7 +493,7 @@ extern "C" int qst_triplet_loss(const float* xa, const float* xp, const float* x
     launch_rows<3>(a, st);
     QST_LAUNCH_CHECK();
     if (reduction != QST_REDUCE_NONE) {
-        tuple_reduce_kernel<<<1, 1024, 0, st>>>(scratch, B, reduction == QST_REDUCE_MEAN ? 1.0f / (float)B : 1.0f, out_loss);
+        row_sum_kernel<float><<<1, 1024, 0, st>>>(scratch, B, reduction == QST_REDUCE_MEAN ? 1.0f / (float)B : 1.0f, out_loss);
         QST_LAUNCH_CHECK();
     }
     return QST_OK;
@@ -552,11 +506,9 @@ extern "C" int qst_quadruplet_eval(const float* xa, const float* xp, const float
     QuadEvalArgs a = {};
     a.x[0] = xa; a.x[1] = xp; a.x[2] = xq; a.x[3] = xn;
     a.dist = out_dist; a.flags = out_flags; a.B = B; a.D = D;
-    bool vec = D % 4 == 0;
-    for (int k = 0; k < 4; ++k) vec = vec && ((uintptr_t)a.x[k] & 15) == 0;
-    const int grid = (int)(((int64_t)B + 3) / 4);
-    if (vec) quad_eval_kernel<true><<<grid, 256, 0, st>>>(a);
-    else quad_eval_kernel<false><<<grid, 256, 0, st>>>(a);
+    const bool vec = D % 4 == 0 && al16(xa) && al16(xp) && al16(xq) && al16(xn);
+    if (vec) quad_eval_kernel<true><<<row_grid(B), 256, 0, st>>>(a);
+    else quad_eval_kernel<false><<<row_grid(B), 256, 0, st>>>(a);
     QST_LAUNCH_CHECK();
     // second stage: one workgroup over the flags, in stream order behind the first
     quad_count_kernel<<<1, 1024, 0, st>>>(out_flags, B, out_counts);

@@ -70,3 +70,53 @@ def cos_matrix(a, b):
     """The fp64 cosine of every pair of rows, numpy."""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return (a / np.linalg.norm(a, axis=1, keepdims=True)) @ (b / np.linalg.norm(b, axis=1, keepdims=True)).T
+
+
+# ------------------------------------------------------------------ what the GPU tests of these kernels share
+SIMS = (H.DOT, H.COS_SIM)
+
+
+def mse_rel_bound(D):
+    """The a-priori relative bound of qst_embed_mse's value. Every term (x - t)^2 is non-negative, so the error of the sum
+    is at most the largest relative error a term can pick up on its way into it:
+      2   the difference is rounded once, and it enters squared
+      1   the square (none if it is fused into the addition that follows)
+      D/64 + 4   the additions of a lane's chain: a lane holds at most 4 * ceil(D / 256) <= D/64 + 4 elements
+      6   the wave tree: four DPP steps and two levels over the four row totals
+      1   the division by B * D and the rounding of the result to fp32
+    each within 2^-24 relative, + 1 for their second-order terms and for the second stage, which adds the row sums in
+    double (2^-53 each)."""
+    return (D / 64 + 15) * U
+
+
+def margin_labels(q, p, n, sim, seed):
+    """The teacher's margins: the yardstick's own margin of the row plus a disagreement of 0.5 .. 1.5 times the scale of
+    the similarity, sign alternating. A residual m - y that cancels to nearly nothing has a gradient 2 (m - y) dm/dx whose
+    RELATIVE error is err(m) / |m - y| in any fp32 evaluation, without bound as the residual goes to 0; this keeps every
+    residual at half the similarity's scale or more (asserted by the callers: a condition on the test data)."""
+    B, D = q.shape
+    g = torch.Generator().manual_seed(seed)
+    scale = 1.0 if (sim == H.COS_SIM or D == 384) else D ** 0.5      # H.rows: unit rows at D = 384, raw randn elsewhere
+    sign = 1.0 - 2.0 * (torch.arange(B) % 2).double()
+    m = margin_ref(q.double(), p.double(), n.double(), sim)
+    y = (m - sign * scale * (0.5 + torch.rand(B, generator=g, dtype=torch.float64))).float()
+    assert ((m - y.double()).abs() >= 0.49 * scale).all()
+    return y
+
+
+def margin_bounds(q, p, n, y, sim):
+    """(bound on m [B], bound on the row value (m - y)^2 [B]), a priori: each similarity within the bound the project holds
+    it to (sim_bound), one rounding for their difference, one for the residual, one for the square."""
+    m = margin_ref(q.double(), p.double(), n.double(), sim)
+    e = m - y.double()
+    dm = sim_bound(q, p, sim) + sim_bound(q, n, sim) + U * m.abs()
+    de = dm + U * (e.abs() + dm)
+    return dm, 2 * e.abs() * de + de ** 2 + U * (e.abs() + de) ** 2
+
+
+def reduced_bound(drow, ref, red):
+    """The row bounds through the second stage (double: nothing to add) and the one rounding of the result to fp32."""
+    if red == 0:
+        return drow
+    total = drow.sum() / (drow.numel() if red == 2 else 1)
+    return total + U * (ref.detach().abs() + total)

@@ -15,6 +15,8 @@ pytestmark = pytest.mark.gpu
 import quadruplet_sentence_transformer_amd  # noqa: E402,F401
 import distill_helpers as DH  # noqa: E402
 import tuple_loss_helpers as H  # noqa: E402
+from distill_helpers import (SIMS, U, margin_bounds, margin_labels, mse_rel_bound, reduced_bound)  # noqa: E402
+from tuple_loss_helpers import RED, check_grads, dev, f64, upstream  # noqa: E402
 from kernel_helpers import lib, ptr, stream  # noqa: E402,F401
 from quadruplet_sentence_transformer_amd import st_losses as S, util  # noqa: E402
 from quadruplet_sentence_transformer_amd.data import ParallelSentencesDataset  # noqa: E402
@@ -22,82 +24,10 @@ from quadruplet_sentence_transformer_amd.evaluation import MSEEvaluator, Transla
 from quadruplet_sentence_transformer_amd.sentence_transformer import (InputExample, SentenceTransformer,  # noqa: E402
                                                                       encode_columns_fused)
 
-RED = (("none", 0), ("sum", 1), ("mean", 2))
 BAD_ARG = -1
-U = DH.U
 # B = 1; the element-by-element path (D % 4 != 0); D past 2048, where the rows no longer stay in registers; 2500 rows = three
 # trips of the 1024-row second stage, the last one partial, on both load paths
 SHAPES = H.SHAPES + [(2500, 33), (2500, 64)]
-SIMS = (H.DOT, H.COS_SIM)
-
-
-def dev(t):
-    return t.cuda().contiguous()
-
-
-def f64(xs):
-    return [t.double().clone().requires_grad_(True) for t in xs]
-
-
-def upstream(B, red):
-    """A non-trivial upstream gradient, as test_gpu_tuple_losses uses."""
-    return torch.linspace(0.5, 1.5, B) if red == 0 else torch.tensor([1.7])
-
-
-def check_grads(grads, xs, skip_rows=None):
-    """test_gpu_tuple_losses.check_grads: its tolerance."""
-    for gi, xi in zip(grads, xs):
-        got, ref = gi.cpu().double(), xi.grad
-        assert torch.isfinite(got).all()
-        if skip_rows is not None:
-            got, ref = got[~skip_rows], ref[~skip_rows]
-        torch.testing.assert_close(got, ref, rtol=1e-4, atol=1e-6)
-
-
-def mse_rel_bound(D):
-    """The a-priori relative bound of qst_embed_mse's value. Every term (x - t)^2 is non-negative, so the error of the sum
-    is at most the largest relative error a term can pick up on its way into it:
-      2   the difference is rounded once, and it enters squared
-      1   the square (none if it is fused into the addition that follows)
-      D/64 + 4   the additions of a lane's chain: a lane holds at most 4 * ceil(D / 256) <= D/64 + 4 elements
-      6   the wave tree: four DPP steps and two levels over the four row totals
-      1   the division by B * D and the rounding of the result to fp32
-    each within 2^-24 relative, + 1 for their second-order terms and for the second stage, which adds the row sums in
-    double (2^-53 each)."""
-    return (D / 64 + 15) * U
-
-
-def margin_labels(q, p, n, sim, seed):
-    """The teacher's margins: the yardstick's own margin of the row plus a disagreement of 0.5 .. 1.5 times the scale of
-    the similarity, sign alternating. A residual m - y that cancels to nearly nothing has a gradient 2 (m - y) dm/dx whose
-    RELATIVE error is err(m) / |m - y| in any fp32 evaluation, without bound as the residual goes to 0; this keeps every
-    residual at half the similarity's scale or more (asserted by the callers: a condition on the test data)."""
-    B, D = q.shape
-    g = torch.Generator().manual_seed(seed)
-    scale = 1.0 if (sim == H.COS_SIM or D == 384) else D ** 0.5      # H.rows: unit rows at D = 384, raw randn elsewhere
-    sign = 1.0 - 2.0 * (torch.arange(B) % 2).double()
-    m = DH.margin_ref(q.double(), p.double(), n.double(), sim)
-    y = (m - sign * scale * (0.5 + torch.rand(B, generator=g, dtype=torch.float64))).float()
-    assert ((m - y.double()).abs() >= 0.49 * scale).all()
-    return y
-
-
-def margin_bounds(q, p, n, y, sim):
-    """(bound on m [B], bound on the row value (m - y)^2 [B]), a priori: each similarity within the bound the project holds
-    it to (DH.sim_bound), one rounding for their difference, one for the residual, one for the square."""
-    m = DH.margin_ref(q.double(), p.double(), n.double(), sim)
-    e = m - y.double()
-    dm = DH.sim_bound(q, p, sim) + DH.sim_bound(q, n, sim) + U * m.abs()
-    de = dm + U * (e.abs() + dm)
-    return dm, 2 * e.abs() * de + de ** 2 + U * (e.abs() + de) ** 2
-
-
-def reduced_bound(drow, ref, red):
-    """The row bounds through the second stage (double: nothing to add) and the one rounding of the result to fp32."""
-    if red == 0:
-        return drow
-    total = drow.sum() / (drow.numel() if red == 2 else 1)
-    return total + U * (ref.detach().abs() + total)
 
 
 # ------------------------------------------------------------------ 1. kernel parity

@@ -36,7 +36,7 @@ def b16(op, *shape):
 
 
 # ------------------------------------------------------------------ loss
-# the last two shapes take quad_loss_reduce_kernel's one-workgroup loop (1024 rows a trip) past its first trip: the first row
+# the last two shapes take row_sum_kernel's one-workgroup loop (1024 rows a trip) past its first trip: the first row
 # of a second trip on the vector path, and a third, partial trip on the scalar path (D % 4 != 0). (Row 1024 of the first is
 # worth more than the sum's tolerance only with swap, 0.99 ... 1.42; the second carries over half of its sum past row 1024.)
 @pytest.mark.parametrize("B,D", [(1, 10), (5, 10), (8, 384), (64, 384), (32, 768), (7, 33), (3, 2052), (1025, 64), (2500, 33)])

@@ -14,45 +14,17 @@ pytestmark = pytest.mark.gpu
 
 import quadruplet_sentence_transformer_amd  # noqa: E402,F401
 import tuple_loss_helpers as H  # noqa: E402
+from tuple_loss_helpers import (RED, check_grads, check_value, dev, f64, margin_between, pair_labels,  # noqa: E402
+                                upstream)
 from kernel_helpers import lib, ptr, stream  # noqa: E402,F401
 from quadruplet_sentence_transformer_amd import st_losses as S  # noqa: E402
 from quadruplet_sentence_transformer_amd.evaluation import EmbeddingSimilarityEvaluator, SimilarityFunction  # noqa: E402
 from quadruplet_sentence_transformer_amd.sentence_transformer import InputExample, SentenceTransformer  # noqa: E402
 
-RED = (("none", 0), ("sum", 1), ("mean", 2))
 BAD_ARG = -1
-# Past one trip of the one-workgroup second stages (tuple_reduce_kernel, online_select_kernel: 1024 rows a trip): a third,
+# Past one trip of the one-workgroup second stages (row_sum_kernel, online_select_kernel: 1024 rows a trip): a third,
 # partial trip on the scalar path (D % 4 != 0) and on the vector path. Local: H.SHAPES is shared with the host tests.
 LONG_SHAPES = [(2500, 33), (2500, 64)]
-
-
-def dev(t):
-    return t.cuda().contiguous()
-
-
-def f64(xs):
-    return [t.double().clone().requires_grad_(True) for t in xs]
-
-
-def upstream(B, red):
-    """A non-trivial upstream gradient, as test_loss_matches_oracle uses."""
-    return torch.linspace(0.5, 1.5, B) if red == 0 else torch.tensor([1.7])
-
-
-def check_value(out, ref, metric, B, D, red):
-    tol = H.value_tol(metric, D)
-    got = out.cpu().double().view(ref.shape)
-    print(f"  value: max |d| = {(got - ref.detach()).abs().max().item():.3e} (tol {tol:.1e})")
-    torch.testing.assert_close(got, ref.detach(), rtol=tol, atol=tol * (B if red == 1 else 1))
-
-
-def check_grads(grads, xs, skip_rows=None):
-    for gi, xi in zip(grads, xs):
-        got, ref = gi.cpu().double(), xi.grad
-        assert torch.isfinite(got).all()
-        if skip_rows is not None:
-            got, ref = got[~skip_rows], ref[~skip_rows]
-        torch.testing.assert_close(got, ref, rtol=1e-4, atol=1e-6)
 
 
 # ------------------------------------------------------------------ 1. kernel parity
@@ -76,29 +48,6 @@ def test_pair_metric_matches_yardstick(lib, B, D, metric):
     else:
         check_value(out, ref, metric, B, D, 0)
     check_grads(grads, xs)
-
-
-def margin_between(vals, metric, D):
-    """A margin inside the central half of `vals` (the yardstick's distances, or d(a, n) - d(a, p)), in the middle of the widest
-    space between two neighbours there: a good part of the hinges open, the rest closed, and -- a condition on the test data
-    -- no row closer to the hinge's kink than five times the error the project accepts on a distance, where fp32 and fp64
-    could fall on different sides of it."""
-    s = vals.detach().sort().values
-    if len(s) == 1:
-        m = 0.5 * float(s[0])
-    else:
-        lo, hi = (len(s) - 1) // 4, max((len(s) - 1) // 4 + 1, (3 * len(s)) // 4)
-        k = lo + int((s[lo + 1:hi + 1] - s[lo:hi]).argmax())
-        m = 0.5 * float(s[k] + s[k + 1])
-    m = float(torch.tensor(max(0.0, m), dtype=torch.float32))   # as the C ABI's `float margin` holds it: the yardstick's too
-    gap = (vals.detach() - m).abs().min().item()
-    assert gap >= 5 * H.value_tol(metric, D), gap
-    return m
-
-
-def pair_labels(B, kind, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand(B, generator=g) if kind == H.MSE else (torch.arange(B) % 2).float()
 
 
 @pytest.mark.parametrize("B,D", H.SHAPES + LONG_SHAPES)

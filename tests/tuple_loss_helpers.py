@@ -111,3 +111,59 @@ def pearson_np(x, y):
 
 def spearman_np(x, y):
     return pearson_np(rank_avg(x), rank_avg(y))
+
+
+# ------------------------------------------------------------------ what the GPU tests of these kernels share
+RED = (("none", 0), ("sum", 1), ("mean", 2))
+
+
+def dev(t):
+    return t.cuda().contiguous()
+
+
+def f64(xs):
+    return [t.double().clone().requires_grad_(True) for t in xs]
+
+
+def upstream(B, red):
+    """A non-trivial upstream gradient, as test_loss_matches_oracle uses."""
+    return torch.linspace(0.5, 1.5, B) if red == 0 else torch.tensor([1.7])
+
+
+def check_value(out, ref, metric, B, D, red):
+    tol = value_tol(metric, D)
+    got = out.cpu().double().view(ref.shape)
+    print(f"  value: max |d| = {(got - ref.detach()).abs().max().item():.3e} (tol {tol:.1e})")
+    torch.testing.assert_close(got, ref.detach(), rtol=tol, atol=tol * (B if red == 1 else 1))
+
+
+def check_grads(grads, xs, skip_rows=None):
+    for gi, xi in zip(grads, xs):
+        got, ref = gi.cpu().double(), xi.grad
+        assert torch.isfinite(got).all()
+        if skip_rows is not None:
+            got, ref = got[~skip_rows], ref[~skip_rows]
+        torch.testing.assert_close(got, ref, rtol=1e-4, atol=1e-6)
+
+
+def margin_between(vals, metric, D):
+    """A margin inside the central half of `vals` (the yardstick's distances, or d(a, n) - d(a, p)), in the middle of the widest
+    space between two neighbours there: a good part of the hinges open, the rest closed, and -- a condition on the test data
+    -- no row closer to the hinge's kink than five times the error the project accepts on a distance, where fp32 and fp64
+    could fall on different sides of it."""
+    s = vals.detach().sort().values
+    if len(s) == 1:
+        m = 0.5 * float(s[0])
+    else:
+        lo, hi = (len(s) - 1) // 4, max((len(s) - 1) // 4 + 1, (3 * len(s)) // 4)
+        k = lo + int((s[lo + 1:hi + 1] - s[lo:hi]).argmax())
+        m = 0.5 * float(s[k] + s[k + 1])
+    m = float(torch.tensor(max(0.0, m), dtype=torch.float32))   # as the C ABI's `float margin` holds it: the yardstick's too
+    gap = (vals.detach() - m).abs().min().item()
+    assert gap >= 5 * value_tol(metric, D), gap
+    return m
+
+
+def pair_labels(B, kind, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.rand(B, generator=g) if kind == MSE else (torch.arange(B) % 2).float()
