@@ -168,8 +168,21 @@ typedef struct {
     int32_t ranges_per_xcd;       /* filled by the library */
     int32_t tiles[QST_TN_MAX_PROB];
     QstGemmArgs prob[QST_TN_MAX_PROB];
+    /* Scheduling of the partial-sum flushes (DESIGN.md finding 47); results differ only in the grouping of the fp32 sums.
+     * Both fields sit at the end, so a library built before them reads a valid prefix of this struct. */
+    int32_t skew;                 /* with one range per XCD, range x is base + off(x) * skew stages of 64 rows long, off = -4, -3,
+                                     -2, -1, +1, +2, +3, +4: the XCDs reach their flushes at different times. 0 = the library's
+                                     choice, > 0 = that many stages (clamped so that the shortest range keeps one stage; 0 with
+                                     more than one range per XCD), < 0 = equal ranges */
+    int32_t order;                /* 0 = the library's choice, 1 = every workgroup reduces its whole tiles first and its piece of
+                                     a leftover tile last, 2 = the workgroups with an odd piece index run that piece first */
 } QstTnGroup;
 int qst_gemm_tn_group(const QstTnGroup* grp, void* stream);
+/* Host only, no device needed: the M-ranges qst_gemm_tn_group's tiled kernel will use for grp (only nprob and the M, N, K of
+ * the problems are read): range r reduces rows [row_begin[r], row_begin[r + 1]); row_begin holds splits + 1 entries, splits
+ * rounded up to a multiple of 8 (8 for 0). Returns the skew in effect (auto value resolved, clamp applied; >= 0) or a
+ * negative QST_ERR_*. The launch and this function share one range function. */
+int qst_tn_group_ranges(const QstTnGroup* grp, int32_t* row_begin);
 
 /* The same GEMMs on the 8-wave, 8-phase K loop (csrc/gemm8p.h, csrc/gemm8.hip): one 512-thread workgroup per CU, 128 KB of
  * LDS, K-tiles of 64 with three half-tiles of LDS-DMA in flight across the barriers. qst_gemm_nt / qst_gemm_tn_group take

@@ -67,7 +67,8 @@ class QstLnReduceBatch(C.Structure):
 class QstTnGroup(C.Structure):
     _fields_ = [("nprob", C.c_int32), ("splits", C.c_int32), ("total_tiles", C.c_int32), ("ranges_per_xcd", C.c_int32),
                 ("tiles", C.c_int32 * 8),
-                ("prob", QstGemmArgs * 8)]
+                ("prob", QstGemmArgs * 8),
+                ("skew", C.c_int32), ("order", C.c_int32)]
 
 
 # name -> (restype, argtypes). Every symbol the two public headers declare.
@@ -135,6 +136,7 @@ SIGNATURES = {
     "qst_ffn_chain": (C.c_int, [C.POINTER(QstFfnArgs), C.POINTER(QstLnEpi), C.c_int, vp]),
     "qst_gemm_tn": (C.c_int, [C.POINTER(QstGemmArgs), vp]),
     "qst_gemm_tn_group": (C.c_int, [C.POINTER(QstTnGroup), vp]),
+    "qst_tn_group_ranges": (C.c_int, [C.POINTER(QstTnGroup), c_i32p]),
     "qst_gemm_nt8_supported": (C.c_int, [C.POINTER(QstGemmArgs), C.c_int]),
     "qst_gemm_nt8": (C.c_int, [C.POINTER(QstGemmArgs), C.c_int, C.c_int, vp]),
     "qst_gemm_tn8_group": (C.c_int, [C.POINTER(QstTnGroup), vp]),

@@ -13,11 +13,13 @@
 //   gemm_nt_f8_kernel   both operands MXFP8 on v_mfma_scale_f32_32x32x64_f8f6f4, 128-deep stages (QST_PREC_FP8, inference)
 //   gemm_nt_ln_kernel<MODE, DROPW>  128x384 full-row tile with the LayerNorm (forward) / LayerNorm backward in the epilogue
 //   gemm_tn_group_kernel            all weight gradients of a layer in one launch, 192x192 tiles, one M-range per XCD,
-//                       4 MFMA + 4 loader waves, 3-slot ring of 64-row stages, float-atomic flush
+//                       4 MFMA + 4 loader waves, 3-slot ring of 64-row stages, float-atomic flush; the ranges are skewed
+//                       and half of the leftover pieces run first, so that the flushes do not all come together
 //   quant_mx_kernel     MXFP8 quantisation of an activation matrix
 // LDS images are XOR-swizzled (applied on the DMA SOURCE address, the destination is lane-linear) so that
 // ds_read_b128 (nt) and ds_read_b64_tr_b16 (tn) fragment reads are bank-conflict-free; LDS-DMA = buffer_load_dwordx4 ... lds
 // (no staging registers, hardware range check zero-fills ragged M / N).
+#include <type_traits>
 #include "qst_common.h"
 #include "qst_kernels.h"
 
@@ -972,6 +974,15 @@ __device__ __forceinline__ int tn_swz(int row) { return ((row >> 1) & 1) << 2; }
 __device__ __forceinline__ uint32_t tn_off(int row, int chunk) {
     return (uint32_t)(row * 384 + ((chunk ^ tn_swz(row)) << 4));
 }
+// c + a + b in fp32 with one instruction (a dot product with (1, 1))
+__device__ __forceinline__ float add_pair(op16 a, op16 b, float c) {
+    const op16x2 v = {a, b}, one = {(op16)1.0f, (op16)1.0f};
+#if QST_OP_F16
+    return __builtin_amdgcn_fdot2(v, one, c, false);
+#else
+    return __builtin_amdgcn_fdot2_f32_bf16(v, one, c, false);
+#endif
+}
 __device__ __forceinline__ op16x4 lds_tr16(const char* p) {
     return lds_tr16_op(p);
 }
@@ -979,6 +990,28 @@ __device__ __forceinline__ op16x4 lds_tr16(const char* p) {
 __device__ __forceinline__ op16x4 lds_tr16_at(uint32_t a) {
     typedef __attribute__((ext_vector_type(4))) __bf16 raw4;
     return __builtin_bit_cast(op16x4, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) raw4*)(uintptr_t)a));
+}
+
+// M-range plan, shared by the kernel, the launch and qst_tn_group_ranges: the ceil(M / 64) stages of 64 rows are dealt out to
+// the ranges in order, whole stages each (the last stage of the last range may be ragged), the remainder to the LAST ranges --
+// so with M >= 64 * splits no range is shorter than 64 rows, and with fewer stages than ranges the first ranges are empty.
+// skew > 0 (one range per XCD only; the launch resolves and clamps it): range x is off(x) * skew stages longer, off = -4, -3,
+// -2, -1, +1, +2, +3, +4, so the eight XCDs arrive at their flushes (fp32 atomics during which a workgroup neither loads
+// nor multiplies, and which run at ONE chip-wide rate) one after the other instead of together.
+// Returns the first stage of range r, r in [0, splits]; range r = rows [64 * stage(r), 64 * stage(r + 1)) cut at M.
+__host__ __device__ inline int tn_range_stage(int stages, int splits, int skew, int r) {
+    const int base = stages / splits, extra = stages % splits;
+    int s = r * base + (r > splits - extra ? r - (splits - extra) : 0);
+    if (skew > 0 && splits == 8) {
+        const int m = r < 8 - r ? r : 8 - r;
+        s -= skew * (m * (9 - m) / 2);                    // off summed over the ranges before r: 0, -4, -7, -9, -10, -9, -7, -4, 0
+    }
+    return s;
+}
+// the largest skew that leaves range 0 (the shortest: base - 4 * skew stages) one stage
+__host__ __device__ inline int tn_skew_max(int stages, int splits) {
+    const int base = stages / splits;
+    return splits == 8 && base > 1 ? (base - 1) / 4 : 0;
 }
 
 // Wave roles: waves 0-3 run the MFMAs (one per SIMD), waves 4-7 are loaders that issue every LDS-DMA (waves 4,5: the two
@@ -991,6 +1024,15 @@ __device__ __forceinline__ op16x4 lds_tr16_at(uint32_t a) {
 // = a*W + b, every workgroup reduces `a` whole tiles and then one stage-piece of a leftover tile (task list in the
 // kernel), so all CUs finish together instead of 1.5 tiles per CU being rounded up to 2; split tiles simply receive
 // several partial sums through the fp32 atomics.
+//
+// Flush scheduling (DESIGN.md finding 47). With equal ranges and every workgroup walking the same task list, all 256
+// workgroups flush at the same moments: the chip alternates between reading and adding. Two things spread the flushes:
+// the ranges are skewed (tn_range_stage: XCD x reduces off(x) * skew stages more, so XCD 0 flushes first and XCD 7 last),
+// and with order 2 the workgroups with an odd leftover-piece index run that piece before their whole tile. Per launch at
+// M = 32,768 (equal ranges, whole tiles first and the earlier bias sums -> skew 2, order 2, bias sums as below): 151.7 ->
+// 137.9 us for a MiniLM layer; H = 768 (six whole tiles per workgroup, no leftover) takes skew 1: 541 -> 479 us. The
+// longest range costs what the skew adds to it (4 * skew stages per tile): skew 4 is back to -3.5%, skew 6 is slower
+// than equal ranges.
 __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1001,8 +1043,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
     const int range = xcd + 8 * (jloc / wg_per_range);             // which M-range
     const int jr = jloc % wg_per_range;                            // workgroup index inside the range
     const int M = grp.prob[0].M;
-    const int per = (((M + grp.splits - 1) / grp.splits) + TBK - 1) / TBK * TBK;
-    const int mbeg = range * per, mend = min(M, mbeg + per);
+    const int stages_m = (M + TBK - 1) / TBK;
+    const int mbeg = min(M, TBK * tn_range_stage(stages_m, grp.splits, grp.skew, range));
+    const int mend = min(M, TBK * tn_range_stage(stages_m, grp.splits, grp.skew, range + 1));
     if (mbeg >= mend) return;
     const int S = (mend - mbeg + TBK - 1) / TBK;                   // stages per tile in this range
     // Task list of this workgroup (W = workgroups per range, T = tiles = a*W + b):
@@ -1013,7 +1056,15 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
     const int W = wg_per_range, T = grp.total_tiles;
     const int a_full = T / W, b_left = T % W;
     const int pieces = b_left > 0 ? max(1, W / b_left) : 1;
-    const int ntasks = a_full + ((b_left > 0 && jr / pieces < b_left) ? 1 : 0);
+    // order 1: workgroups jr = t * pieces + pc take piece pc of leftover tile t, after their whole tiles.
+    // order 2: jr = lp * b_left + lt takes piece lp of leftover tile lt -- the workgroups of one piece index are neighbours and
+    //   walk the same stages together -- and those with an odd lp run that piece BEFORE their whole tiles: half of the range
+    //   flushes while the other half reads, instead of the whole range alternating between reading and adding.
+    const bool by_piece = grp.order == 2 && b_left > 0;
+    const int lt = by_piece ? jr % b_left : jr / pieces, lp = by_piece ? jr / b_left : jr % pieces;
+    const bool has_left = b_left > 0 && (by_piece ? lp < pieces : lt < b_left);
+    const bool left_first = by_piece && has_left && (lp & 1);
+    const int ntasks = a_full + (has_left ? 1 : 0);
 
     // transposed-read lane geometry (cdna guide T10): lane i = 4q+p of a 16-lane group supplies row q, cols 4p..4p+3
     const int li = lane & 15, q = li >> 2, p = li & 3, gsel = (lane >> 4) & 1, fh = lane >> 5;
@@ -1022,15 +1073,15 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
 #pragma unroll 1
     for (int task = 0; task < ntasks; ++task) {
         int tile, s0, s1;
-        if (task < a_full) { tile = task * W + jr; s0 = 0; s1 = S; }
+        const int wt = left_first ? (task == 0 ? a_full : task - 1) : task;     // whole tile wt, or wt == a_full: the piece
+        if (wt < a_full) { tile = wt * W + jr; s0 = 0; s1 = S; }
         else {
-            tile = a_full * W + jr / pieces;
-            const int pc = jr % pieces;
+            tile = a_full * W + lt;
             const int per_piece = (S + pieces - 1) / pieces;
-            s0 = pc * per_piece; s1 = min(S, s0 + per_piece);
+            s0 = lp * per_piece; s1 = min(S, s0 + per_piece);
         }
         const int nm = s1 - s0;
-        if (nm <= 0) continue;                                     // uniform over the workgroup
+        if (nm <= 0) continue;                                     // uniform over the workgroup (an empty piece, in either order)
         int pi = 0;
 #pragma unroll 1
         while (pi + 1 < grp.nprob && tile >= grp.tiles[pi]) { tile -= grp.tiles[pi]; ++pi; }
@@ -1103,7 +1154,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
             for (int j = 0; j < 3; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        const bool do_bias = (g.colsum != nullptr) && (k0 == 0) && (wn == 0);
+        // bias gradient: the waves of the tiles with k0 == 0 sum the dY fragments they read anyway; the two waves that read
+        // the same fragments (wn = 0, 1) take the even and the odd k-steps
+        const bool do_bias = (g.colsum != nullptr) && (k0 == 0);
         // Fragment-read addresses: read (ks, i, jj) of a stage is at slot + la[i] + (ks * 16 + 4 * jj) * 384 -- the swizzle of
         // its row is the lane's alone (row bit 1 = q bit 1: ks * 16, 8 * fh and 4 * jj leave it), so three lane offsets per
         // operand and an immediate cover the 48 reads of a stage: six adds per stage instead of one or two per read.
@@ -1118,6 +1171,14 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
         }
         uint32_t slot = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;      // of stage mt: mt % TSTAGES
 
+        // The stage loop exists once per bias role (chosen once per task; BIAS = 0: none, 1: the even k-steps, 2: the odd
+        // ones): a branch on it inside a stage cuts the stage into scheduling regions and the pinned order below holds only
+        // inside each, so the waves that also sum the bias fragments ran the compiler's order (all reads of a k-step, wait,
+        // multiply) -- and summed with a convert and an add per element, 192 VALU instructions per stage on two of the four
+        // waves: the launch was 4% (H = 384) and 13% (H = 768) faster without colsum. Now v_dot2c_f32_{bf16,f16} against
+        // (1, 1) adds two elements per instruction and each wave sums half of the k-steps: 24 per stage.
+        auto run_stages = [&](auto bias_tag) __attribute__((always_inline)) {
+        constexpr int BIAS = decltype(bias_tag)::value;
         for (int mt = 0; mt < nm; ++mt) {
             __builtin_amdgcn_s_barrier();                  // stage mt landed (the loaders waited for it before arriving)
             uint32_t ra[3], rb[3];
@@ -1142,46 +1203,49 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_group_kernel(QstTnGroup grp) {
             }                                                                                               \
         }                                                                                                   \
     } while (0)
-#define TN_MFMA(set_)                                                                                       \
+#define TN_MFMA(ks_, set_)                                                                                    \
     do {                                                                                                    \
         _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                       \
             _Pragma("unroll") for (int j = 0; j < 3; ++j)                                                   \
                 acc[i][j] = mfma32_op(fa[set_][i], fb[set_][j], acc[i][j]); \
-        if (do_bias) {   /* lane (n' = lane&31, half h) holds dY[m = 8h .. 8h+7][n']: 8 of the 16 rows of this k-step */ \
+        if (BIAS == 1 + ((ks_) & 1)) {   /* lane (n' = lane&31, half h) holds dY[m = 8h .. 8h+7][n']: 8 of the 16 rows of this k-step */ \
             _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                   \
-                _Pragma("unroll") for (int e = 0; e < 8; ++e) bsum[i] += (float)fa[set_][i][e];             \
+                _Pragma("unroll") for (int e = 0; e < 8; e += 2) bsum[i] = add_pair(fa[set_][i][e], fa[set_][i][e + 1], bsum[i]); \
         }                                                                                                   \
     } while (0)
             TN_LOAD(0, 0);
             TN_LOAD(1, 1);
-            TN_MFMA(0);
+            TN_MFMA(0, 0);
             TN_LOAD(2, 0);
-            TN_MFMA(1);
+            TN_MFMA(1, 1);
             TN_LOAD(3, 1);
-            TN_MFMA(0);
-            TN_MFMA(1);
+            TN_MFMA(2, 0);
+            TN_MFMA(3, 1);
 #undef TN_LOAD
 #undef TN_MFMA
-            if (!do_bias) {
-                // issue order: the 12 reads of k-step 0; then the 12 reads of each later k-step spread behind the 9 MFMAs of the
-                // k-step before it (two behind each of the first three, one behind each of the other six); then the last 9 MFMAs
-                __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
+            // issue order: the 12 reads of k-step 0; then the 12 reads of each later k-step spread behind the 9 MFMAs of the
+            // k-step before it (two behind each of the first three, one behind each of the other six); then the last 9 MFMAs.
+            // The bias adds (12 per k-step that has them) are left to the scheduler: they depend on nothing but their fragments.
+            __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
 #pragma unroll
-                for (int rep = 0; rep < 3; ++rep) {
+            for (int rep = 0; rep < 3; ++rep) {
 #pragma unroll
-                    for (int u = 0; u < 3; ++u) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 6; ++u) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
+                for (int u = 0; u < 3; ++u) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
                 }
-                __builtin_amdgcn_sched_group_barrier(0x008, 9, 0);
+#pragma unroll
+                for (int u = 0; u < 6; ++u) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
             }
+            __builtin_amdgcn_sched_group_barrier(0x008, 9, 0);
         }
+        };
+        if (!do_bias) run_stages(std::integral_constant<int, 0>{});
+        else if (wn == 0) run_stages(std::integral_constant<int, 1>{});
+        else run_stages(std::integral_constant<int, 2>{});
         __builtin_amdgcn_s_barrier();                      // end of piece: the loaders may refill the ring while we flush
 
         float* C = (float*)g.C;
@@ -1406,6 +1470,52 @@ extern "C" int QST_K(qst_gemm_nt_ln)(const QstGemmArgs* a, const QstLnEpi* ln, i
 
 static bool tn8_auto(const QstTnGroup* g) { (void)g; return false; }
 
+// The library's choice of QstTnGroup.skew and .order (DESIGN.md finding 47; per-launch sweeps at M = 8,192 ... 196,608 in
+// profiles/r07_ab_wgrad_phase.txt), by shape class: T tiles on the 32 workgroups of a range, `base` stages per equal range.
+//   fewer than two tiles per workgroup (a MiniLM layer: 48 tiles, one whole tile and half a leftover one each -- every
+//   workgroup flushes twice, all of them together): skew 2, best at base = 32 and 64, within 1.5% of skew 1 at base = 16;
+//   more (an H = 768 layer: 192 tiles, six flushes each): skew 1 -- the imbalance a skew costs grows with the tiles per
+//   workgroup, and skew 2 already loses at base = 16.
+// Ranges shorter than 16 stages (M < 8,192) and launches with fewer tiles than workgroups were not measured and keep equal
+// ranges and the whole tiles first. Order 2 changes nothing where no tile is left over or the leftover tiles are not cut.
+static int tn_auto_skew(int total_tiles, int base) { return base < 16 || total_tiles < 32 ? 0 : total_tiles < 64 ? 2 : 1; }
+static int tn_auto_order(int total_tiles, int base) { return base < 16 || total_tiles < 32 ? 1 : 2; }
+
+// Fills what the library owns in *g -- tiles, total_tiles, splits, ranges_per_xcd -- and resolves skew (>= 0, clamped) and
+// order (1 or 2). launch: the operands are checked as well (qst_tn_group_ranges reads the shapes only).
+static int tn_plan(QstTnGroup* g, bool launch) {
+    if (g->nprob <= 0 || g->nprob > QST_TN_MAX_PROB) return QST_ERR_BAD_ARG;
+    g->total_tiles = 0;
+    for (int i = 0; i < g->nprob; ++i) {
+        const QstGemmArgs& a = g->prob[i];
+        if ((launch && (!a.A || !a.B || !a.C)) || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.M != g->prob[0].M) return QST_ERR_BAD_ARG;
+        if ((launch && (a.lda % 8 != 0 || a.ldb % 8 != 0)) || a.N % 8 != 0 || a.K % 8 != 0) return QST_ERR_UNSUPPORTED;
+        if (launch && ((int64_t)a.M * a.lda * 2 >= 0x7FFFFF00LL || (int64_t)a.M * a.ldb * 2 >= 0x7FFFFF00LL)) return QST_ERR_UNSUPPORTED;
+        g->tiles[i] = ((a.N + TT - 1) / TT) * ((a.K + TT - 1) / TT);
+        g->total_tiles += g->tiles[i];
+    }
+    // one M-range per XCD (every operand row leaves HBM once) unless the caller asks for more
+    if (g->splits <= 0) g->splits = 8;
+    g->splits = (g->splits + 7) / 8 * 8;
+    g->ranges_per_xcd = g->splits / 8;
+    const int stages_m = (g->prob[0].M + TBK - 1) / TBK, base = stages_m / g->splits;
+    if (g->skew == 0) g->skew = tn_auto_skew(g->total_tiles, base);
+    g->skew = g->skew < 0 ? 0 : std::min(g->skew, tn_skew_max(stages_m, g->splits));
+    if (g->order != 1 && g->order != 2) g->order = tn_auto_order(g->total_tiles, base);
+    return QST_OK;
+}
+
+#if !QST_OP_F16      // (host arithmetic, the same for both operand types: exported once)
+extern "C" int qst_tn_group_ranges(const QstTnGroup* grp_in, int32_t* row_begin) {
+    if (!grp_in || !row_begin) return QST_ERR_BAD_ARG;
+    QstTnGroup g = *grp_in;
+    if (int rc = tn_plan(&g, false)) return rc;
+    const int M = g.prob[0].M, stages_m = (M + TBK - 1) / TBK;
+    for (int r = 0; r <= g.splits; ++r) row_begin[r] = std::min(M, TBK * tn_range_stage(stages_m, g.splits, g.skew, r));
+    return g.skew;
+}
+#endif
+
 extern "C" int QST_K(qst_gemm_tn_group)(const QstTnGroup* grp_in, void* stream) {
     if (!grp_in || grp_in->nprob <= 0 || grp_in->nprob > QST_TN_MAX_PROB) return QST_ERR_BAD_ARG;
     {
@@ -1413,25 +1523,11 @@ extern "C" int QST_K(qst_gemm_tn_group)(const QstTnGroup* grp_in, void* stream) 
         if (mode >= 0 ? (mode & 2) != 0 : tn8_auto(grp_in)) return QST_K(qst_gemm_tn8_group)(grp_in, stream);
     }
     QstTnGroup g = *grp_in;
-    g.total_tiles = 0;
-    for (int i = 0; i < g.nprob; ++i) {
-        const QstGemmArgs& a = g.prob[i];
-        if (!a.A || !a.B || !a.C || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.M != g.prob[0].M) return QST_ERR_BAD_ARG;
-        if (a.lda % 8 != 0 || a.ldb % 8 != 0 || a.N % 8 != 0 || a.K % 8 != 0) return QST_ERR_UNSUPPORTED;
-        if ((int64_t)a.M * a.lda * 2 >= 0x7FFFFF00LL || (int64_t)a.M * a.ldb * 2 >= 0x7FFFFF00LL) return QST_ERR_UNSUPPORTED;
-        g.tiles[i] = ((a.N + TT - 1) / TT) * ((a.K + TT - 1) / TT);
-        g.total_tiles += g.tiles[i];
-    }
+    if (int rc = tn_plan(&g, true)) return rc;
     const int M = g.prob[0].M;
-    if (g.splits <= 0) {
-        // one M-range per XCD (every operand row leaves HBM once); a second range per XCD only when the ranges are
-        // long enough that 32 workgroups per range still get >= 8 stages of work each
-        g.splits = 8;
-    }
-    g.splits = (g.splits + 7) / 8 * 8;
-    g.ranges_per_xcd = g.splits / 8;
-    // 32 workgroups per XCD (one per CU) share each XCD's ranges; never more workgroups than (tile, stage) pairs
-    const int64_t stages = ((int64_t)(M + g.splits - 1) / g.splits + TBK - 1) / TBK;
+    // 32 workgroups per XCD (one per CU) share each XCD's ranges; never more workgroups than (tile, stage) pairs of the longest range
+    const int stages_m = (M + TBK - 1) / TBK;
+    const int64_t stages = tn_range_stage(stages_m, g.splits, g.skew, g.splits) - tn_range_stage(stages_m, g.splits, g.skew, g.splits - 1);
     int64_t wg_per_range = 32 / g.ranges_per_xcd;
     if (wg_per_range < 1) wg_per_range = 1;
     const int64_t work = (int64_t)g.total_tiles * stages;
