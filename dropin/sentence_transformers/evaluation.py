@@ -1,5 +1,6 @@
 from quadruplet_sentence_transformer_amd.evaluation import (EmbeddingSimilarityEvaluator,  # noqa: F401
-                                                            InformationRetrievalEvaluator, MSEEvaluator,
+                                                            InformationRetrievalEvaluator, LabelAccuracyEvaluator,
+                                                            MSEEvaluator,
                                                             ParaphraseMiningEvaluator,
                                                             QuadrupletEvaluator,
                                                             QuadrupletLossEvaluator, SentenceEvaluator,

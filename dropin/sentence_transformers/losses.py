@@ -1,9 +1,9 @@
-"""sentence_transformers.losses: the pair, triplet, in-batch-negatives, batch-mining triplet and distillation objectives on the HIP
-path (st_losses.py)."""
+"""sentence_transformers.losses: the pair, triplet, in-batch-negatives, batch-mining triplet, distillation and
+softmax-classifier objectives on the HIP path (st_losses.py)."""
 from quadruplet_sentence_transformer_amd.st_losses import (BatchAllTripletLoss, BatchHardSoftMarginTripletLoss,  # noqa: F401
                                                            BatchHardTripletLoss, BatchHardTripletLossDistanceFunction,
                                                            BatchSemiHardTripletLoss, ContrastiveLoss, CosineSimilarityLoss,
                                                            MarginMSELoss, MSELoss, MultipleNegativesRankingLoss,
                                                            MultipleNegativesSymmetricRankingLoss,
-                                                           OnlineContrastiveLoss, SiameseDistanceMetric,
+                                                           OnlineContrastiveLoss, SiameseDistanceMetric, SoftmaxLoss,
                                                            TripletDistanceMetric, TripletLoss)

@@ -415,6 +415,59 @@ int qst_clip_adamw_step_amp(const qst_encoder* enc, float* params, float* grads,
                             int64_t* step_dev, float* scaler_dev, float growth_factor, float backoff_factor,
                             int32_t growth_interval, float* norm_out, float* scratch, void* stream);
 
+/* qst_clip_adamw_step over the arena AND a second flat fp32 buffer that lives outside it (version 108): parameters a loss
+ * owns, such as the classifier of losses.SoftmaxLoss (loss_params.py). The extra group has the arena's conventions: x_n
+ * elements, a multiple of 256; every tensor padded with zeros to a multiple of 256; x_chunk_decay one flag per 256-element
+ * chunk (device). norm_out is the L2 norm over both buffers together -- what clip_grad_norm_(loss_model.parameters()) sees --
+ * and one clip coefficient, lr and step apply to both; AdamW and zero_grad run on both. x_n == 0 (the x_ pointers are then
+ * not looked at) gives the bits of qst_clip_adamw_step. x_n % 256 != 0, x_n < 0 or a NULL x_ pointer with x_n > 0:
+ * QST_ERR_BAD_ARG before any launch. scratch: fp32 [2048]. */
+int qst_clip_adamw_step_joint(const qst_encoder* enc, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                              float* x_params, float* x_grads, float* x_exp_avg, float* x_exp_avg_sq,
+                              const uint8_t* x_chunk_decay, int64_t x_n,
+                              float lr, float beta1, float beta2, float eps, float weight_decay,
+                              float max_grad_norm, float grad_scale, int64_t step,
+                              float* norm_out, float* scratch, void* stream);
+
+/*
+ * The classifier of sentence-transformers 2.2.2's losses.SoftmaxLoss (version 108; csrc/softmax_head.hip): a Linear on the
+ * concatenation [u, v, |u - v|, u * v] of two sentence embeddings, its cross entropy, and their backward. All fp32, no
+ * atomics, every sum in a fixed order (the same inputs give the same bits), on the caller's stream without host
+ * synchronisation.
+ *   u, v   : f32 [B, D], contiguous, 16-byte aligned
+ *   parts  : which parts are concatenated, a mask of QST_SOFTMAX_*; their order is always u, v, |u - v|, u * v
+ *   w      : f32 [C, K], K = (2 with REP + 1 with DIFF + 1 with MULT) * D, torch.nn.Linear layout, 16-byte aligned; b f32 [C]
+ * 1 <= C <= 8, D % 4 == 0, D <= 2048: anything else QST_ERR_UNSUPPORTED. parts outside 1 .. 7, B < 1, a NULL or unaligned
+ * pointer: QST_ERR_BAD_ARG. Both before any launch, nothing written. The feature vector [B, K] is never materialised.
+ */
+enum { QST_SOFTMAX_REP = 1, QST_SOFTMAX_DIFF = 2, QST_SOFTMAX_MULT = 4 };
+/* logits f32 [B, C] = features W^T + b. One wave per row; the rows of u and v stay in registers. */
+int qst_softmax_head_fwd(const float* u, const float* v, const float* w, const float* b, int B, int D, int C, int parts,
+                         float* logits, void* stream);
+/* From dlogits f32 [B, C]: grad_u, grad_v f32 [B, D], grad_w f32 [C, K], grad_b f32 [C], all written (not accumulated).
+ * d|u - v| uses sign(u - v) with sign(0) = 0, torch's abs gradient. The weight gradient walks the rows in order, in up to 32
+ * slices of at least 64 rows whose partial sums (in `workspace`, 16-byte aligned, qst_softmax_head_bwd_workspace_bytes; 0
+ * bytes up to B = 64) are added in the order of the slices. */
+size_t qst_softmax_head_bwd_workspace_bytes(int B, int D, int C, int parts);
+int qst_softmax_head_bwd(const float* u, const float* v, const float* w, const float* dlogits, int B, int D, int C, int parts,
+                         float* grad_u, float* grad_v, float* grad_w, float* grad_b, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* torch.nn.CrossEntropyLoss(weight=None, label_smoothing=0, ignore_index, reduction) on logits f32 [B, C] (any C >= 1) and
+ * labels int64 [B]. A row whose label equals ignore_index contributes 0, has zero gradients and is left out of the mean's
+ * denominator (no row left: the mean is NaN, as in torch). Any other label outside [0, C) gives NaN for its row's loss and
+ * gradients -- where torch asserts on the device -- and counts in the mean's denominator; a label is compared, never used
+ * as an index.
+ *   out_loss : f32 [B] (QST_REDUCE_NONE) or [1]
+ *   dlogits  : f32 [B, C] or NULL = forward only: (softmax - onehot) [/ kept rows], times grad_out (device; [B] for
+ *              QST_REDUCE_NONE, [1] otherwise; NULL = ones)
+ *   counts   : int64 [2] or NULL: {rows with a label in range, rows among them whose largest logit is the label's}; among
+ *              equal logits the lowest index is the argmax
+ *   scratch  : f32 [B + 2], 8-byte aligned
+ * Under QST_REDUCE_MEAN each row's value is divided by the number of kept rows (in double, rounded to fp32) before the
+ * shared second stage sums the rows in double. */
+int qst_softmax_ce(const float* logits, const int64_t* labels, int B, int C, int64_t ignore_index, int reduction,
+                   float* out_loss, const float* grad_out, float* dlogits, int64_t* counts, float* scratch, void* stream);
+
 /* Retrieval scoring for the encode()-driven evaluators: what sentence-transformers'
  * InformationRetrievalEvaluator does per corpus chunk -- util.cos_sim / util.dot_score of the query embeddings
  * against the chunk, then torch.topk(k) (reference call sites models/evaluators.py:572-588,

@@ -248,7 +248,8 @@ class CrossEncoder:
         raise NotImplementedError("CrossEncoder.fit: cross-encoder training is not part of this build. What surrounds it is: a "
                                   "new head on a bare encoder (num_labels=...), smart_batching_collate, save() / "
                                   "save_pretrained() and the evaluators of cross_encoder_evaluation; the training step itself "
-                                  "(the head's training forward and backward, the loss, the joint optimiser step) is not")
+                                  "(the head's training forward and backward, the loss) is not; the joint optimiser step over "
+                                  "encoder and head is HipEncoder.adamw_step(extra=...)")
 
     # ---- saving: a directory transformers' AutoModelForSequenceClassification and CrossEncoder(path) both load
     def state_dict(self) -> Dict[str, torch.Tensor]:

@@ -39,6 +39,23 @@ __global__ __launch_bounds__(1024) void norm_finish_kernel(const float* partial,
     }
 }
 
+// The norm over two buffers (qst_clip_adamw_step_joint): thread i adds partial i of the extra group to partial i of the arena,
+// then the tree of norm_finish_kernel. nx == 0 adds nothing, and the result has norm_finish_kernel's bits.
+__global__ __launch_bounds__(1024) void norm_finish_joint_kernel(const float* partial, int n, const float* xpartial, int nx,
+                                                                 float grad_scale, float* norm_out) {
+    __shared__ float red[16];
+    float s = threadIdx.x < n ? partial[threadIdx.x] : 0.f;
+    if (threadIdx.x < nx) s += xpartial[threadIdx.x];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float v = threadIdx.x < 16 ? red[threadIdx.x] : 0.f;
+        v = wave_sum(v);
+        if (threadIdx.x == 0) norm_out[0] = sqrtf(v) * fabsf(grad_scale);
+    }
+}
+
 // Device-side schedule (graph-capturable step: no per-step host value reaches a kernel argument). One thread advances
 // the step counter and derives this step's learning rate (transformers.get_linear_schedule_with_warmup, as
 // trainer.warmup_linear_lr) and Adam bias corrections into dyn[0..2] = {lr, 1-beta1^t, sqrt(1-beta2^t)}.
@@ -205,6 +222,51 @@ extern "C" int qst_adamw_launch(float* params, float* grads, float* exp_avg, flo
     a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     adamw_kernel<<<2048, 256, 0, st>>>(a);
     QST_LAUNCH_CHECK();
+    return QST_OK;
+}
+
+// qst_clip_adamw_step_joint: the step of qst_adamw_launch over the arena and over a second flat buffer with the arena's
+// conventions (a multiple of 256 elements, one decay flag per 256-element chunk), clipped on the norm of both together.
+extern "C" int qst_adamw_launch_joint(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                                      const uint8_t* chunk_decay, int64_t n, float* x_params, float* x_grads,
+                                      float* x_exp_avg, float* x_exp_avg_sq, const uint8_t* x_chunk_decay, int64_t x_n,
+                                      float lr, float beta1, float beta2, float eps, float weight_decay,
+                                      float max_grad_norm, float grad_scale, int64_t step, float* norm_out, float* scratch,
+                                      hipStream_t st) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !chunk_decay || n <= 0 || (n & 255) || step < 1)
+        return QST_ERR_BAD_ARG;
+    if (x_n < 0 || (x_n & 255)) return QST_ERR_BAD_ARG;
+    if (x_n > 0 && (!x_params || !x_grads || !x_exp_avg || !x_exp_avg_sq || !x_chunk_decay)) return QST_ERR_BAD_ARG;
+    const int64_t xn4 = x_n / 4;
+    if (max_grad_norm > 0.f || norm_out) {
+        if (!norm_out || !scratch) return QST_ERR_BAD_ARG;
+        sumsq_kernel<<<kNormBlocks, 256, 0, st>>>(grads, n / 4, scratch);
+        QST_LAUNCH_CHECK();
+        const int xblocks = (int)(xn4 < (int64_t)kNormBlocks * 256 ? (xn4 + 255) / 256 : kNormBlocks);
+        if (xblocks > 0) {
+            sumsq_kernel<<<xblocks, 256, 0, st>>>(x_grads, xn4, scratch + kNormBlocks);
+            QST_LAUNCH_CHECK();
+        }
+        norm_finish_joint_kernel<<<1, 1024, 0, st>>>(scratch, kNormBlocks, scratch + kNormBlocks, xblocks, grad_scale, norm_out);
+        QST_LAUNCH_CHECK();
+    }
+    AdamArgs a;
+    a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.chunk_decay = chunk_decay;
+    a.dyn = nullptr; a.amp = 0;
+    a.norm = (max_grad_norm > 0.f) ? norm_out : nullptr;
+    a.n4 = n / 4;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay; a.max_norm = max_grad_norm;
+    a.grad_scale = grad_scale;
+    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    adamw_kernel<<<2048, 256, 0, st>>>(a);
+    QST_LAUNCH_CHECK();
+    if (x_n > 0) {                  // the same coefficient, learning rate and step on the extra group
+        a.p = x_params; a.g = x_grads; a.m = x_exp_avg; a.v = x_exp_avg_sq; a.chunk_decay = x_chunk_decay;
+        a.n4 = xn4;
+        adamw_kernel<<<(int)(xn4 < 2048 * 256 ? (xn4 + 255) / 256 : 2048), 256, 0, st>>>(a);
+        QST_LAUNCH_CHECK();
+    }
     return QST_OK;
 }
 

@@ -15,7 +15,7 @@
 static thread_local int g_last_hip_error = 0;
 extern "C" int qst_set_hip_error(int code) { g_last_hip_error = code; return code; }
 extern "C" int qst_last_hip_error(void) { return g_last_hip_error; }
-extern "C" int qst_version(void) { return 107; }
+extern "C" int qst_version(void) { return 108; }
 
 extern "C" const char* qst_strerror(int s) {
     switch (s) {
@@ -1243,6 +1243,17 @@ extern "C" int qst_clip_adamw_step(const qst_encoder* e, float* params, float* g
     if (!e) return QST_ERR_BAD_ARG;
     return qst_adamw_launch(params, grads, exp_avg, exp_avg_sq, e->chunk_decay, e->lay.total, lr, beta1, beta2, eps,
                             weight_decay, max_grad_norm, grad_scale, step, norm_out, scratch, (hipStream_t)stream);
+}
+
+extern "C" int qst_clip_adamw_step_joint(const qst_encoder* e, float* params, float* grads, float* exp_avg,
+                                         float* exp_avg_sq, float* x_params, float* x_grads, float* x_exp_avg,
+                                         float* x_exp_avg_sq, const uint8_t* x_chunk_decay, int64_t x_n, float lr,
+                                         float beta1, float beta2, float eps, float weight_decay, float max_grad_norm,
+                                         float grad_scale, int64_t step, float* norm_out, float* scratch, void* stream) {
+    if (!e) return QST_ERR_BAD_ARG;
+    return qst_adamw_launch_joint(params, grads, exp_avg, exp_avg_sq, e->chunk_decay, e->lay.total, x_params, x_grads,
+                                  x_exp_avg, x_exp_avg_sq, x_chunk_decay, x_n, lr, beta1, beta2, eps, weight_decay,
+                                  max_grad_norm, grad_scale, step, norm_out, scratch, (hipStream_t)stream);
 }
 
 extern "C" int64_t qst_abi_sizeof(int which) {

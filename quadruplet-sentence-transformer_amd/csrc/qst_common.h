@@ -45,6 +45,12 @@ extern "C" int qst_adamw_launch(float* params, float* grads, float* exp_avg, flo
                                 const uint8_t* chunk_decay, int64_t n, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, float max_grad_norm, float grad_scale, int64_t step,
                                 float* norm_out, float* scratch, hipStream_t st);
+extern "C" int qst_adamw_launch_joint(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                                      const uint8_t* chunk_decay, int64_t n, float* x_params, float* x_grads,
+                                      float* x_exp_avg, float* x_exp_avg_sq, const uint8_t* x_chunk_decay, int64_t x_n,
+                                      float lr, float beta1, float beta2, float eps, float weight_decay,
+                                      float max_grad_norm, float grad_scale, int64_t step, float* norm_out, float* scratch,
+                                      hipStream_t st);
 extern "C" int qst_adamw_launch_sched(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
                                       const uint8_t* chunk_decay, int64_t n, float base_lr, float beta1, float beta2,
                                       float eps, float weight_decay, float max_grad_norm, float grad_scale,

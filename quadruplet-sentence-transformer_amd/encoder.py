@@ -347,10 +347,25 @@ class HipEncoder:
             ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), "qst_encoder_backward")
 
     def adamw_step(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
-                   max_grad_norm: float = 1.0, grad_scale: float = 1.0) -> None:
-        """clip_grad_norm_ + AdamW + zero_grad in one pass over the arena; the norm stays on the device."""
+                   max_grad_norm: float = 1.0, grad_scale: float = 1.0, extra=None) -> None:
+        """clip_grad_norm_ + AdamW + zero_grad in one pass over the arena; the norm stays on the device. `extra`: a
+        loss_params.LossParameters on this device, clipped on the joint norm and stepped with the arena
+        (qst_clip_adamw_step_joint); None makes the call it always made."""
+        if extra is not None and extra.ensure().device != self.device:
+            raise _lib.QstError(f"adamw_step: the extra parameters live on {extra.device}, the encoder on {self.device}")
         self.opt_step += 1
-        self._clip_adamw("qst_clip_adamw_step", lr, betas, eps, weight_decay, max_grad_norm, grad_scale, self.opt_step)
+        if extra is None:
+            self._clip_adamw("qst_clip_adamw_step", lr, betas, eps, weight_decay, max_grad_norm, grad_scale, self.opt_step)
+            return
+        extra.ensure_state()
+        self.ensure_train_state()
+        _lib.check(self.lib.qst_clip_adamw_step_joint(
+            self.handle, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+            extra.params.data_ptr(), extra.grads.data_ptr(), extra.exp_avg.data_ptr(), extra.exp_avg_sq.data_ptr(),
+            extra.chunk_decay.data_ptr(), extra.total, lr, betas[0], betas[1], eps, weight_decay, max_grad_norm, grad_scale,
+            self.opt_step, self.grad_norm.data_ptr(), self._scratch.data_ptr(), _lib.current_stream_ptr()),
+            "qst_clip_adamw_step_joint")
+        self.mark_stale()
 
     def _clip_adamw(self, entry: str, lr, betas, eps, weight_decay, max_grad_norm, grad_scale, *extra) -> None:
         """What the three optimiser steps share: the arenas and AdamW arguments in front of an entry point's own (`extra`),

@@ -3,7 +3,8 @@
 TripletEvaluator and InformationRetrievalEvaluator, whose scoring + top-k run on the GPU
 through libqst (util.topk_scores), EmbeddingSimilarityEvaluator (graded pairs; qst_pair_metric) and
 ParaphraseMiningEvaluator (util.paraphrase_mining on the streaming top-k, qst_topk_stream), and the two that go with a
-distillation, MSEEvaluator (qst_embed_mse) and TranslationEvaluator (two k = 1 searches of the streaming top-k). The two
+distillation, MSEEvaluator (qst_embed_mse) and TranslationEvaluator (two k = 1 searches of the streaming top-k), and
+LabelAccuracyEvaluator, which scores the classifier of losses.SoftmaxLoss (qst_softmax_ce's counts). The two
 evaluators the reference selects its models with, QuadrupletEvaluator (qst_quadruplet_eval) and QuadrupletLossEvaluator, and the chain
 get_sequential_evaluator builds of them stand at the end."""
 from __future__ import annotations
@@ -577,6 +578,44 @@ class TranslationEvaluator(SentenceEvaluator):
         if output_path is not None and self.write_csv:
             _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers, [epoch, steps, acc_src2trg, acc_trg2src])
         return (acc_src2trg + acc_trg2src) / 2
+
+
+class LabelAccuracyEvaluator(SentenceEvaluator):
+    """sentence-transformers 2.2.2's LabelAccuracyEvaluator: the share of a labelled dataset on which the largest logit of
+    `softmax_model` (a losses.SoftmaxLoss; called with labels=None it returns the logits) is the label's. `dataloader` yields
+    InputExamples with two texts and an integer label. The hits of every batch are counted by a forward-only qst_softmax_ce
+    (st_losses.label_counts), summed on the device and read back once; among equal logits the lowest index is the
+    prediction, as torch.argmax returns it."""
+
+    def __init__(self, dataloader, name: str = "", softmax_model=None, write_csv: bool = True):
+        self.dataloader = dataloader
+        self.name = name
+        self.softmax_model = softmax_model
+        self.write_csv = write_csv
+        self.csv_file = "accuracy_evaluation" + ("_" + name if name else "") + "_results.csv"
+        self.csv_headers = ["epoch", "steps", "accuracy"]
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1) -> float:
+        import torch
+        from . import st_losses as S
+        from .sentence_transformer import batch_to_device
+        model.eval()
+        self.dataloader.collate_fn = model.smart_batching_collate
+        total, hits = 0, None
+        for features, label_ids in self.dataloader:
+            features = [batch_to_device(f, model.device) for f in features]
+            label_ids = label_ids.to(model.device)
+            with torch.no_grad():
+                _, prediction = self.softmax_model(features, labels=None)
+                counts = S.label_counts(prediction, label_ids)
+            total += prediction.size(0)
+            hits = counts[1:2].clone() if hits is None else hits + counts[1:2]
+        correct = int(hits.item()) if hits is not None else 0
+        accuracy = correct / total if total else 0.0
+        LOGGER.info("Accuracy on %s: %.4f (%d/%d)", self.name, accuracy, correct, total)
+        if output_path is not None and self.write_csv:
+            _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers, [epoch, steps, accuracy])
+        return accuracy
 
 
 def _unwrap_example(example):

@@ -492,6 +492,23 @@ class SentenceTransformer(nn.Module):
         if data_parallel != "off" and dist.is_available() and dist.is_initialized():
             world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
         dp_mode = (data_parallel or "split_batch") if world > 1 else "off"
+        # a loss that owns parameters outside the arena (owned_parameters() -> loss_params.LossParameters: SoftmaxLoss's
+        # classifier) is clipped and stepped with the encoder by enc.adamw_step(extra=...); what has no joint form refuses here
+        owned = [lm.owned_parameters() if hasattr(lm, "owned_parameters") else None for lm in loss_models]
+        for lm, op in zip(loss_models, owned):
+            if op is None:
+                continue
+            why = None
+            if amp:
+                why = f"precision={precision!r} / use_amp: the mixed-precision optimiser step has no joint form yet"
+            elif world > 1:
+                why = f"a data-parallel world of {world}: the loss's own gradients are not exchanged between the ranks"
+            elif resume_from_checkpoint is not None:
+                why = "resume_from_checkpoint: checkpoints hold the encoder only, not the loss's parameters and moments"
+            if why is not None:
+                raise NotImplementedError(f"fit(): {type(lm).__name__} trains parameters of its own, which is not supported "
+                                          f"with {why}")
+            op.ensure().zero_grad()
         self._dp = None if world == 1 else {"group": process_group, "buckets": gradient_buckets(self.cfg),
                                             "overlap": bool(overlap_grad_reduce)}
         self._dp_works, self._dp_reduced, self._live_graphs = [], False, 0
@@ -566,7 +583,8 @@ class SentenceTransformer(nn.Module):
                             enc.adamw_step_amp(lr, int(warmup_steps), t_total if sched == "warmuplinear" else 0, betas, eps,
                                                weight_decay, float(max_grad_norm), 1.0 / world)
                         else:
-                            enc.adamw_step(lr_at(global_step), betas, eps, weight_decay, float(max_grad_norm), 1.0 / world)
+                            enc.adamw_step(lr_at(global_step), betas, eps, weight_decay, float(max_grad_norm), 1.0 / world,
+                                           extra=owned[idx])
                     training_steps += 1
                     global_step += 1
                     if evaluation_steps > 0 and training_steps % evaluation_steps == 0:

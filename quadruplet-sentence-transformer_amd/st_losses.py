@@ -40,6 +40,10 @@ embedding of each example as its label ([B, D]: SentenceTransformer.smart_batchi
 `util.pairwise_cos_sim` -- recognised by identity, like the similarity functions above -- the two similarities, their
 difference, the squared error and all three gradients are one qst_margin_mse_loss call; any other callable
 `f(a, b) -> [B]` is called on the embeddings and the rest runs in torch.
+
+`SoftmaxLoss` is the one objective here with parameters of its own: an `nn.Linear` classifier on [u, v, |u - v|, u * v] whose
+weights live in a `loss_params.LossParameters`, a flat buffer the fused optimiser step takes next to the arena. Logits, cross
+entropy and all four gradients are csrc/softmax_head.hip (qst_softmax_head_fwd, qst_softmax_ce, qst_softmax_head_bwd).
 """
 from __future__ import annotations
 
@@ -49,6 +53,7 @@ import torch
 from torch import nn
 
 from . import _lib, util
+from .loss_params import LossParameters
 from .sentence_transformer import encode_columns_fused
 
 # include/qst.h
@@ -294,6 +299,15 @@ class _MarginMseFn(torch.autograd.Function):
     def backward(ctx, grad_output):
         _, grads = margin_mse_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
         return (*[g.to(dt) for g, dt in zip(grads, ctx.in_dtypes)], None, None, None)
+
+
+def _device_of(model) -> torch.device:
+    """Where a model's tensors live: its `device`, else that of its first parameter, else the CPU (a stand-in without any)."""
+    dev = getattr(model, "device", None)
+    if isinstance(dev, (str, torch.device)):
+        return torch.device(dev)
+    first = next(iter(model.parameters()), None) if isinstance(model, nn.Module) else None
+    return first.device if first is not None else torch.device("cpu")
 
 
 def _require_rows(what: str, *xs) -> None:
@@ -794,3 +808,186 @@ class MarginMSELoss(_TupleLoss):
             return margin_mse(q, p, n, labels.view(-1), sim, "mean")
         margin = self.similarity_fct(q, p) - self.similarity_fct(q, n)
         return torch.nn.functional.mse_loss(margin, labels.view(-1).to(margin.dtype))
+
+
+# ------------------------------------------------------------------ SoftmaxLoss: a classifier the loss owns and trains
+SOFTMAX_REP, SOFTMAX_DIFF, SOFTMAX_MULT = 1, 2, 4          # QST_SOFTMAX_*: the parts of the classifier's input
+_HEAD_MAX_C, _HEAD_MAX_D = 8, 2048
+
+
+def softmax_head_supported(D: int, C: int, parts: int) -> bool:
+    """Whether qst_softmax_head_fwd / _bwd take this shape (include/qst.h)."""
+    return 1 <= C <= _HEAD_MAX_C and D % 4 == 0 and 4 <= D <= _HEAD_MAX_D and 1 <= parts <= 7
+
+
+def softmax_head_fwd_raw(u, v, w, b, parts: int) -> torch.Tensor:
+    """qst_softmax_head_fwd on contiguous fp32 HIP tensors u, v [B, D], w [C, K], b [C]: the logits [B, C]."""
+    lib = _lib.load()
+    (B, D), C = u.shape, w.shape[0]
+    logits = torch.empty(B, C, dtype=torch.float32, device=u.device)
+    with torch.cuda.device(u.device):
+        _lib.check(lib.qst_softmax_head_fwd(u.data_ptr(), v.data_ptr(), w.data_ptr(), b.data_ptr(), B, D, C, int(parts),
+                                            logits.data_ptr(), _lib.current_stream_ptr()), "qst_softmax_head_fwd")
+    return logits
+
+
+def softmax_head_bwd_raw(u, v, w, dlogits, parts: int):
+    """qst_softmax_head_bwd: (grad_u, grad_v [B, D], grad_w [C, K], grad_b [C]) from dlogits [B, C]."""
+    lib = _lib.load()
+    (B, D), C = u.shape, w.shape[0]
+    gu, gv = _grad_slabs(2, u, True)
+    gw = torch.empty_like(w)
+    gb = torch.empty(C, dtype=torch.float32, device=u.device)
+    nbytes = int(lib.qst_softmax_head_bwd_workspace_bytes(B, D, C, int(parts)))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=u.device)
+    with torch.cuda.device(u.device):
+        _lib.check(lib.qst_softmax_head_bwd(u.data_ptr(), v.data_ptr(), w.data_ptr(), dlogits.data_ptr(), B, D, C, int(parts),
+                                            gu.data_ptr(), gv.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), nbytes,
+                                            _lib.current_stream_ptr()), "qst_softmax_head_bwd")
+    return gu, gv, gw, gb
+
+
+def softmax_ce_raw(logits, labels, reduction: int = 2, ignore_index: int = -100, grad_out: Optional[torch.Tensor] = None,
+                   want_grads: bool = False, want_counts: bool = False):
+    """qst_softmax_ce on contiguous fp32 logits [B, C] and int64 labels [B] (HIP): (loss [B] or [1], dlogits [B, C] or None,
+    counts int64 [2] = {rows with a label in range, rows whose argmax is the label} or None)."""
+    lib = _lib.load()
+    B, C = logits.shape
+    out = torch.empty(B if reduction == 0 else 1, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits) if want_grads else None
+    counts = torch.empty(2, dtype=torch.int64, device=logits.device) if want_counts else None
+    scratch = torch.empty(B + 2, dtype=torch.float32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        _lib.check(lib.qst_softmax_ce(logits.data_ptr(), labels.data_ptr(), B, C, int(ignore_index), int(reduction),
+                                      out.data_ptr(), _lib.ptr(grad_out), _lib.ptr(dlogits), _lib.ptr(counts),
+                                      scratch.data_ptr(), _lib.current_stream_ptr()), "qst_softmax_ce")
+    return out, dlogits, counts
+
+
+class _SoftmaxHeadFn(torch.autograd.Function):
+    """logits = classifier([u, v, |u - v|, u * v]): qst_softmax_head_fwd, and qst_softmax_head_bwd from autograd's dlogits."""
+
+    @staticmethod
+    def forward(ctx, u, v, w, b, parts):
+        xs = _f32((u, v, w, b))
+        logits = softmax_head_fwd_raw(*xs, parts)
+        ctx.save_for_backward(*xs[:3])
+        ctx.parts, ctx.in_dtypes = parts, (u.dtype, v.dtype, w.dtype, b.dtype)
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        u, v, w = ctx.saved_tensors
+        grads = softmax_head_bwd_raw(u, v, w, grad_logits.detach().to(torch.float32).contiguous(), ctx.parts)
+        return (*[g.to(dt) for g, dt in zip(grads, ctx.in_dtypes)], None)
+
+
+class _SoftmaxLossFn(torch.autograd.Function):
+    """nn.CrossEntropyLoss()(classifier([u, v, |u - v|, u * v]), labels): forward = qst_softmax_head_fwd + qst_softmax_ce,
+    backward = qst_softmax_ce (dlogits, times the upstream scalar on the device) + qst_softmax_head_bwd."""
+
+    @staticmethod
+    def forward(ctx, u, v, w, b, labels, parts, ignore_index):
+        xs = _f32((u, v, w, b))
+        y = labels.detach().to(torch.int64).contiguous().reshape(-1)
+        logits = softmax_head_fwd_raw(*xs, parts)
+        out, _, _ = softmax_ce_raw(logits, y, _RED_CODE["mean"], ignore_index)
+        ctx.save_for_backward(*xs[:3], logits, y)
+        ctx.hp, ctx.in_dtypes = (parts, ignore_index), (u.dtype, v.dtype, w.dtype, b.dtype)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        u, v, w, logits, y = ctx.saved_tensors
+        parts, ignore_index = ctx.hp
+        _, dlogits, _ = softmax_ce_raw(logits, y, _RED_CODE["mean"], ignore_index, grad_out=_upstream(grad_output),
+                                       want_grads=True)
+        grads = softmax_head_bwd_raw(u, v, w, dlogits, parts)
+        return (*[g.to(dt) for g, dt in zip(grads, ctx.in_dtypes)], None, None, None)
+
+
+def label_counts(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """int64 [2] on the device: {rows whose label is in [0, C), rows among them whose largest logit is the label's} of logits
+    [B, C] and integer labels [B] (HIP tensors). One forward-only qst_softmax_ce call; among equal logits the lowest index
+    is the prediction, as torch.argmax returns it."""
+    if logits.dim() != 2 or labels.numel() != logits.shape[0]:
+        raise ValueError(f"label_counts: logits {tuple(logits.shape)} need one label per row, {labels.numel()} given")
+    _require_rows("label_counts", logits)
+    _require_labels("label_counts", labels, logits.shape[0])
+    (z,) = _f32((logits,))
+    y = labels.detach().to(torch.int64).contiguous().reshape(-1)
+    return softmax_ce_raw(z, y, _RED_CODE["mean"], want_counts=True)[2]
+
+
+class SoftmaxLoss(_TupleLoss):
+    """sentence-transformers 2.2.2's SoftmaxLoss, the NLI objective: loss_fct(classifier(cat(parts)), labels) with the parts
+    u, v (concatenation_sent_rep), |u - v| (concatenation_sent_difference), u * v (concatenation_sent_multiplication) of the two
+    sentence embeddings, in that order. `classifier` is an nn.Linear built as sentence-transformers builds it (the same
+    torch.manual_seed gives the same initial weights) whose parameters live in a loss_params.LossParameters: fit() finds it
+    through owned_parameters() and clips and steps it together with the encoder. Its state_dict keys are classifier.weight
+    and classifier.bias; save() and the checkpoints of fit() hold the encoder only, as in sentence-transformers.
+
+    With a default-configured nn.CrossEntropyLoss (mean, no class weights, no label smoothing; any ignore_index) the logits,
+    the cross entropy and the gradients for u, v, weight and bias are qst_softmax_head_fwd / qst_softmax_ce /
+    qst_softmax_head_bwd (csrc/softmax_head.hip), fp32. Any other loss_fct is called in torch on the kernels' logits. A shape
+    the kernels do not take (more than 8 labels, an embedding width that is no multiple of 4 or above 2048) runs as torch
+    ops on the same parameter views. forward(sentence_features, labels=None) returns (reps, logits), as 2.2.2 does."""
+    reduction = "mean"
+
+    def __init__(self, model, sentence_embedding_dimension: int, num_labels: int, concatenation_sent_rep: bool = True,
+                 concatenation_sent_difference: bool = True, concatenation_sent_multiplication: bool = False,
+                 loss_fct=nn.CrossEntropyLoss(), fused: bool = True):
+        super().__init__(model, fused)
+        self.num_labels = num_labels
+        self.concatenation_sent_rep = concatenation_sent_rep
+        self.concatenation_sent_difference = concatenation_sent_difference
+        self.concatenation_sent_multiplication = concatenation_sent_multiplication
+        num_vectors_concatenated = 0
+        if concatenation_sent_rep:
+            num_vectors_concatenated += 2
+        if concatenation_sent_difference:
+            num_vectors_concatenated += 1
+        if concatenation_sent_multiplication:
+            num_vectors_concatenated += 1
+        if num_vectors_concatenated == 0:
+            raise ValueError("SoftmaxLoss: at least one of the three concatenation flags must be set")
+        self.classifier = nn.Linear(num_vectors_concatenated * sentence_embedding_dimension, num_labels)
+        self.loss_fct = loss_fct
+        self.sentence_embedding_dimension = sentence_embedding_dimension
+        self._parts = (SOFTMAX_REP if concatenation_sent_rep else 0) | (SOFTMAX_DIFF if concatenation_sent_difference else 0) \
+            | (SOFTMAX_MULT if concatenation_sent_multiplication else 0)
+        self._owned = LossParameters(self.classifier, device=_device_of(model))
+
+    def owned_parameters(self) -> "LossParameters":
+        return self._owned
+
+    def _default_ce(self) -> bool:
+        f = self.loss_fct
+        return type(f) is nn.CrossEntropyLoss and f.weight is None and f.reduction == "mean" \
+            and getattr(f, "label_smoothing", 0.0) == 0.0
+
+    def _features(self, u, v):
+        parts = []
+        if self.concatenation_sent_rep:
+            parts += [u, v]
+        if self.concatenation_sent_difference:
+            parts.append(torch.abs(u - v))
+        if self.concatenation_sent_multiplication:
+            parts.append(u * v)
+        return torch.cat(parts, 1)
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor = None):
+        self._owned.ensure()
+        u, v = self._embed(sentence_features, 2)
+        w, b = self.classifier.weight, self.classifier.bias
+        kernels = u.is_cuda and w.device == u.device and softmax_head_supported(u.shape[1], self.num_labels, self._parts)
+        if labels is not None and kernels and self._default_ce():
+            _require_labels("SoftmaxLoss", labels, u.shape[0])
+            return _SoftmaxLossFn.apply(u, v, w, b, labels.view(-1), self._parts, int(self.loss_fct.ignore_index))
+        if kernels:
+            output = _SoftmaxHeadFn.apply(u, v, w, b, self._parts)
+        else:
+            output = torch.nn.functional.linear(self._features(u, v), w, b)
+        if labels is None:
+            return [u, v], output
+        return self.loss_fct(output, labels.view(-1))
