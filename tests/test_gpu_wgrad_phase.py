@@ -9,17 +9,12 @@ The exact cases draw the operands from the integers -2 .. 2: every product and e
 4 * 2560 < 2^24, so fp32 sums are exact in any grouping and the result must EQUAL the reference -- a row counted twice or
 dropped at a moved boundary changes an element by up to 4, far inside the tolerance above.
 """
-import ctypes as C
-import functools
-import math
-
 import pytest
-import torch
 
 pytestmark = pytest.mark.gpu
 
-from quadruplet_sentence_transformer_amd import _lib  # noqa: E402
-from kernel_helpers import OPDT, kf, lib, op, opr, stream  # noqa: E402,F401
+import wgrad_helpers  # noqa: E402
+from kernel_helpers import kf, lib, op  # noqa: E402,F401
 
 LAYER = [(384, 1536), (1536, 384), (384, 384), (1152, 384)]         # dW2, dW1, dWo, dWqkv of a MiniLM layer: 48 tiles
 
@@ -32,45 +27,12 @@ def tiled(lib):
     lib.qst_gemm8_mode(-1)
 
 
-@functools.lru_cache(maxsize=None)
-def problem(op, M, N, K, ints=False):
-    """dY [M, N] and X [M, K] in the operand type on the device, dY^T . X and the column sums of dY (fp32, CPU)"""
-    g = torch.Generator().manual_seed(M * 3 + N + K + (7 if ints else 0))
-    if ints:
-        A = torch.randint(-2, 3, (M, N), generator=g).float()
-        B = torch.randint(-2, 3, (M, K), generator=g).float()
-    else:
-        A = opr(op, torch.randn(M, N, generator=g))
-        B = opr(op, torch.randn(M, K, generator=g))
-    return A.to(OPDT[op]).cuda(), B.to(OPDT[op]).cuda(), A.t() @ B, A.sum(0)
-
-
-def run(lib, op, M, shapes, skew, order, launches=1, preset=0.0, ints=False):
-    grp = _lib.QstTnGroup()
-    grp.nprob, grp.splits, grp.skew, grp.order = len(shapes), 0, skew, order
-    outs = []
-    for i, (N, K) in enumerate(shapes):
-        Ad, Bd, ref, rcs = problem(op, M, N, K, ints)
-        Cd = torch.full((N, K), preset, device="cuda")             # accumulation semantics: C += A^T . B
-        cs = torch.zeros(N, device="cuda")
-        q = grp.prob[i]
-        q.A, q.B, q.C, q.colsum = Ad.data_ptr(), Bd.data_ptr(), Cd.data_ptr(), cs.data_ptr()
-        q.M, q.N, q.K, q.lda, q.ldb, q.ldc = M, N, K, N, K, K
-        outs.append((Cd, cs, launches * ref + preset, launches * rcs))
-    for _ in range(launches):
-        _lib.check(kf(lib, "qst_gemm_tn_group", op)(grp, stream()))
-    torch.cuda.synchronize()
-    rtol, atol = (0.0, 0.0) if ints else (1e-3, launches * 1e-3 * math.sqrt(M))
-    for Cd, cs, ref, rcs in outs:
-        torch.testing.assert_close(Cd.cpu(), ref, rtol=rtol, atol=atol)
-        torch.testing.assert_close(cs.cpu(), rcs, rtol=rtol, atol=atol)
-    return grp
+def run(lib, op, M, shapes, skew, order, **kw):
+    return wgrad_helpers.run(kf(lib, "qst_gemm_tn_group", op), op, M, shapes, skew, order, **kw)
 
 
 def effective_skew(lib, grp):
-    begins = (C.c_int32 * 9)()
-    eff = lib.qst_tn_group_ranges(grp, begins)
-    return eff, list(begins)
+    return wgrad_helpers.effective_skew(lib.qst_tn_group_ranges, grp)
 
 
 @pytest.mark.parametrize("order", [1, 2])
