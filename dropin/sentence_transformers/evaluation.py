@@ -1,4 +1,5 @@
-from quadruplet_sentence_transformer_amd.evaluation import (EmbeddingSimilarityEvaluator,  # noqa: F401
+from quadruplet_sentence_transformer_amd.evaluation import (BinaryClassificationEvaluator,  # noqa: F401
+                                                            EmbeddingSimilarityEvaluator,
                                                             InformationRetrievalEvaluator, LabelAccuracyEvaluator,
                                                             MSEEvaluator,
                                                             ParaphraseMiningEvaluator,

@@ -468,6 +468,31 @@ int qst_softmax_head_bwd(const float* u, const float* v, const float* w, const f
 int qst_softmax_ce(const float* logits, const int64_t* labels, int B, int C, int64_t ignore_index, int reduction,
                    float* out_loss, const float* grad_out, float* dlogits, int64_t* counts, float* scratch, void* stream);
 
+/*
+ * What sentence-transformers 2.2.2's evaluation.BinaryClassificationEvaluator computes from the scores of n sentence pairs
+ * and their labels in {0, 1} (version 109; csrc/binary_eval.hip), for nsets score rows over the same labels in one call.
+ * With `rows` the stable sort of (score, label) by score -- descending where high_is_similar[set] != 0 (cosine, dot),
+ * ascending otherwise (distances); -0.0 == +0.0 -- and a cut after row i, i = 0 .. n - 2, taking rows[0 .. i] as positive:
+ *   accuracy, accuracy_threshold : the largest (positives before the cut + negatives after it) / n and the mean of the
+ *                                  two scores around that cut (in fp32); no cut above 0 (n == 1 among them): 0 and -1
+ *   f1, precision, recall, f1_threshold : the largest 2 p r / (p + r), p = c / (i + 1), r = c / T (c the positives before
+ *                                  the cut, c > 0; T all positives), evaluated in double in exactly that order; none: all 0
+ *   ap                           : the average precision, (1 / T) * sum over the positive pairs of (positives at least as
+ *                                  similar) / (pairs at least as similar), equal scores included; T == 0: 0
+ * Among equal maxima the first cut in sorted order wins; rows inside a run of equal scores are cuts like any other.
+ *   scores : f32 [nsets, n] (device), labels : int64 [n] (device), high_is_similar : int32 [nsets] (HOST)
+ *   out    : f64 [nsets, 8] (device) = {accuracy, accuracy_threshold, f1, precision, recall, f1_threshold, ap, T}
+ * Nothing is sorted: an n x n counting pass gives every pair its place in `rows` and the counts above, and a pass of one
+ * workgroup per set picks the cuts. No atomics, integer counts, the sum of ap in a fixed order (the same inputs give the
+ * same bits), on the caller's stream without host synchronisation. A NaN score has no defined place.
+ * 1 <= n <= 2^20 and 1 <= nsets <= 8: anything larger QST_ERR_UNSUPPORTED. A NULL pointer, n < 1, nsets < 1, a workspace
+ * that is not 16-byte aligned or shorter than qst_binary_eval_workspace_bytes (24 bytes per pair and set; 0 for sizes
+ * outside the limits): QST_ERR_BAD_ARG. Both before any launch, nothing written.
+ */
+size_t qst_binary_eval_workspace_bytes(int64_t n, int nsets);
+int qst_binary_eval(const float* scores, const int64_t* labels, int64_t n, int nsets, const int32_t* high_is_similar,
+                    double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Retrieval scoring for the encode()-driven evaluators: what sentence-transformers'
  * InformationRetrievalEvaluator does per corpus chunk -- util.cos_sim / util.dot_score of the query embeddings
  * against the chunk, then torch.topk(k) (reference call sites models/evaluators.py:572-588,

@@ -114,6 +114,8 @@ SIGNATURES = {
     "qst_softmax_head_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "qst_softmax_head_bwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "qst_softmax_ce": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "qst_binary_eval_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "qst_binary_eval": (C.c_int, [vp, vp, C.c_int64, C.c_int, c_i32p, vp, vp, C.c_size_t, vp]),
     "qst_shadow8_bytes": (C.c_int64, [C.POINTER(QstConfig)]),
     "qst_clip_adamw_step_sched": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                             C.c_float, C.c_float, C.c_int64, C.c_int64, vp, vp, vp, vp]),

@@ -4,7 +4,9 @@ TripletEvaluator and InformationRetrievalEvaluator, whose 
 through libqst (util.topk_scores), EmbeddingSimilarityEvaluator (graded pairs; qst_pair_metric) and
 ParaphraseMiningEvaluator (util.paraphrase_mining on the streaming top-k, qst_topk_stream), and the two that go with a
 distillation, MSEEvaluator (qst_embed_mse) and TranslationEvaluator (two k = 1 searches of the streaming top-k), and
-LabelAccuracyEvaluator, which scores the classifier of losses.SoftmaxLoss (qst_softmax_ce's counts). The two
+LabelAccuracyEvaluator, which scores the classifier of losses.SoftmaxLoss (qst_softmax_ce's counts), and
+BinaryClassificationEvaluator for the contrastive pair losses (best accuracy and F1 cuts and the average precision of
+four pair scores, counted without a sort by qst_binary_eval). The two
 evaluators the reference selects its models with, QuadrupletEvaluator (qst_quadruplet_eval) and QuadrupletLossEvaluator, and the chain
 get_sequential_evaluator builds of them stand at the end."""
 from __future__ import annotations
@@ -616,6 +618,159 @@ class LabelAccuracyEvaluator(SentenceEvaluator):
         if output_path is not None and self.write_csv:
             _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers, [epoch, steps, accuracy])
         return accuracy
+
+
+def _binary_cuts_numpy(scores: np.ndarray, labels: np.ndarray, high_score_more_similar: bool) -> Dict[str, float]:
+    """The best accuracy and F1 cuts of BinaryClassificationEvaluator on the host, in the counting form the kernel uses:
+    the pairs take their places by a stable argsort, the positives before every cut are one cumulative sum, and both
+    searches are a first argmax. The arithmetic is upstream's: the accuracy's count over n, c / e, c / T and
+    2 * p * r / (p + r) in double, the thresholds in the scores' own type."""
+    n = len(scores)
+    res = dict(accuracy=0.0, accuracy_threshold=-1.0, f1=0.0, precision=0.0, recall=0.0, f1_threshold=0.0)
+    if n < 2:
+        return res
+    order = np.argsort(-scores if high_score_more_similar else scores, kind="stable")
+    s, y = scores[order], labels[order]
+    total = int(y.sum())
+    place = np.arange(1, n, dtype=np.int64)                     # pairs taken as positive by the cut behind row i
+    hits = np.cumsum(y)[:-1]                                    # ... and the positives among them
+    count = hits + (n - total) - (place - hits)
+    r = int(np.argmax(count))
+    if count[r] > 0:
+        res["accuracy"] = float(count[r] / n)
+        res["accuracy_threshold"] = float((s[r] + s[r + 1]) / 2)
+    cuts = np.flatnonzero(hits > 0)
+    if len(cuts):
+        c = hits[cuts].astype(np.float64)
+        precision, recall = c / place[cuts], c / float(total)
+        f1 = 2 * precision * recall / (precision + recall)
+        k = int(np.argmax(f1))
+        r = int(cuts[k])
+        res.update(f1=float(f1[k]), precision=float(precision[k]), recall=float(recall[k]),
+                   f1_threshold=float((s[r] + s[r + 1]) / 2))
+    return res
+
+
+class BinaryClassificationEvaluator(SentenceEvaluator):
+    """sentence-transformers 2.2.2's BinaryClassificationEvaluator, the one that goes with losses.ContrastiveLoss and
+    OnlineContrastiveLoss: sentence pairs labelled 1 (similar) or 0, scored by cosine similarity, Manhattan and Euclidean
+    distance and dot product; per score the cut of the sorted pairs with the best accuracy and the one with the best F1
+    (with precision, recall and thresholds) and the average precision. The return value is the largest of the four
+    average precisions. Every distinct sentence is encoded once, the four scores are one qst_pair_metric launch each and
+    stay on the device, where ONE qst_binary_eval call (csrc/binary_eval.hip: an n x n counting pass, no sort) turns them
+    into the 4 x 8 numbers that come back to the host; upstream sorts the pairs and walks them in Python twice per score.
+    Up to 2^20 pairs."""
+
+    _SCORES = ("cossim", "manhattan", "euclidean", "dot")
+    _HIGH_IS_SIMILAR = (True, False, False, True)
+    _METRICS = ("accuracy", "accuracy_threshold", "f1", "precision", "recall", "f1_threshold", "ap")
+
+    def __init__(self, sentences1: List[str], sentences2: List[str], labels: List[int], name: str = "", batch_size: int = 32,
+                 show_progress_bar: bool = False, write_csv: bool = True):
+        self.sentences1, self.sentences2, self.labels = sentences1, sentences2, labels
+        assert len(self.sentences1) == len(self.sentences2)
+        assert len(self.sentences1) == len(self.labels)
+        for label in labels:
+            assert label == 0 or label == 1
+        self.name, self.batch_size, self.write_csv = name, batch_size, write_csv
+        if show_progress_bar is None:
+            show_progress_bar = LOGGER.getEffectiveLevel() in (logging.INFO, logging.DEBUG)
+        self.show_progress_bar = show_progress_bar
+        self.csv_file = "binary_classification_evaluation" + ("_" + name if name else "") + "_results.csv"
+        self.csv_headers = ["epoch", "steps"] + [f"{s}_{m}" for s in self._SCORES for m in self._METRICS]
+
+    @classmethod
+    def from_input_examples(cls, examples, **kwargs):
+        return cls([ex.texts[0] for ex in examples], [ex.texts[1] for ex in examples], [ex.label for ex in examples],
+                   **kwargs)
+
+    def _device_scores(self, model):
+        """fp32 [4, n] on the device, rows in the order of _SCORES; the distances as they are (a smaller one is more
+        similar). The distinct sentences, in first-seen order, go through one encode call."""
+        import torch
+        from . import st_losses as S
+        sentences = list(dict.fromkeys(list(self.sentences1) + list(self.sentences2)))
+        emb = model.encode(sentences, batch_size=self.batch_size, show_progress_bar=self.show_progress_bar,
+                           convert_to_tensor=True)
+        index = {s: i for i, s in enumerate(sentences)}
+        with torch.no_grad():
+            e1 = emb.index_select(0, torch.tensor([index[s] for s in self.sentences1], dtype=torch.int64, device=emb.device))
+            e2 = emb.index_select(0, torch.tensor([index[s] for s in self.sentences2], dtype=torch.int64, device=emb.device))
+            rows = [S.pair_metric(e1, e2, m) for m in (S.METRIC_COS_SIM, S.METRIC_L1_PLAIN, S.METRIC_L2_PLAIN, S.METRIC_DOT)]
+            return torch.stack(rows).to(torch.float32).contiguous()
+
+    def pair_scores(self, model) -> Dict[str, np.ndarray]:
+        """{'cossim', 'manhattan', 'euclidean', 'dot'} -> the score of every pair, fp32 from the device; the two distances
+        are not negated."""
+        return dict(zip(self._SCORES, self._device_scores(model).cpu().numpy()))
+
+    def compute_metrices(self, model) -> Dict[str, Dict[str, float]]:
+        import torch
+        from . import _lib, st_losses as S
+        n = len(self.sentences1)
+        if n > S.BINARY_EVAL_MAX_PAIRS:
+            raise _lib.QstError(f"BinaryClassificationEvaluator: {n} pairs; qst_binary_eval takes up to "
+                                f"{S.BINARY_EVAL_MAX_PAIRS} (2^20)")
+        scores = self._device_scores(model)
+        labels = torch.as_tensor(np.asarray(self.labels, dtype=np.int64), device=scores.device)
+        with torch.no_grad():
+            out = S.binary_eval_raw(scores, labels, self._HIGH_IS_SIMILAR)
+            finite = torch.isfinite(scores).all().to(torch.float64).reshape(1)
+            host = torch.cat([out.reshape(-1), finite]).cpu().numpy()       # the one copy to the host
+        if host[-1] == 0.0:
+            raise ValueError("BinaryClassificationEvaluator: a pair's score is NaN or infinite; such scores have no order")
+        table = host[:-1].reshape(len(self._SCORES), 8)
+        result = {}
+        for name, row in zip(self._SCORES, table):
+            result[name] = {m: float(v) for m, v in zip(self._METRICS, row)}
+            LOGGER.info("%s: accuracy %.2f (threshold %.4f), f1 %.2f (threshold %.4f), precision %.2f, recall %.2f, ap %.2f",
+                        name, row[0] * 100, row[1], row[2] * 100, row[5], row[3] * 100, row[4] * 100, row[6] * 100)
+        return result
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1) -> float:
+        LOGGER.info("Binary accuracy evaluation of the model on %s dataset (epoch %s, steps %s)", self.name, epoch, steps)
+        scores = self.compute_metrices(model)
+        main_score = max(scores[name]["ap"] for name in scores)
+        if output_path is not None and self.write_csv:
+            row = [epoch, steps] + [scores[s][m] for s in self._SCORES for m in self._METRICS]
+            _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers, row)
+        return main_score
+
+    @staticmethod
+    def _best_cuts(scores, labels, high_score_more_similar: bool) -> Dict[str, float]:
+        """Both searches on array-likes (lists, numpy arrays, tensors). float32 scores go through qst_binary_eval when a
+        HIP device is visible and the pairs fit it; anything else (no device, or scores of another type, whose thresholds
+        upstream forms in that type) through the numpy restatement."""
+        import torch
+        from . import st_losses as S
+        to_numpy = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)  # noqa: E731
+        s, y = to_numpy(scores).reshape(-1), to_numpy(labels).reshape(-1)
+        if len(s) != len(y):
+            raise ValueError(f"{len(s)} scores but {len(y)} labels")
+        if not np.issubdtype(s.dtype, np.floating):
+            s = s.astype(np.float64)
+        if not np.isfinite(s).all():
+            raise ValueError("a score is NaN or infinite; such scores have no order")
+        if not np.isin(y, (0, 1)).all():
+            raise ValueError("the labels must be 0 or 1")
+        y = y.astype(np.int64)
+        if s.dtype == np.float32 and 1 <= len(s) <= S.BINARY_EVAL_MAX_PAIRS and torch.cuda.is_available():
+            out = S.binary_eval_raw(torch.from_numpy(np.ascontiguousarray(s)).cuda().view(1, -1),
+                                    torch.from_numpy(np.ascontiguousarray(y)).cuda(), [high_score_more_similar])
+            return dict(zip(BinaryClassificationEvaluator._METRICS, out.cpu().numpy()[0, :6].tolist()))
+        return _binary_cuts_numpy(s, y, bool(high_score_more_similar))
+
+    @staticmethod
+    def find_best_acc_and_threshold(scores, labels, high_score_more_similar: bool):
+        """(the best accuracy, its threshold) of upstream's walk over the sorted pairs."""
+        r = BinaryClassificationEvaluator._best_cuts(scores, labels, high_score_more_similar)
+        return r["accuracy"], r["accuracy_threshold"]
+
+    @staticmethod
+    def find_best_f1_and_threshold(scores, labels, high_score_more_similar: bool):
+        """(the best F1, its precision, its recall, its threshold) of upstream's walk over the sorted pairs."""
+        r = BinaryClassificationEvaluator._best_cuts(scores, labels, high_score_more_similar)
+        return r["f1"], r["precision"], r["recall"], r["f1_threshold"]
 
 
 def _unwrap_example(example):

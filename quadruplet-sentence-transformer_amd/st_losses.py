@@ -864,6 +864,32 @@ def softmax_ce_raw(logits, labels, reduction: int = 2, ignore_index: int = -100,
     return out, dlogits, counts
 
 
+BINARY_EVAL_MAX_PAIRS, BINARY_EVAL_MAX_SETS = 1 << 20, 8       # qst_binary_eval's limits (include/qst.h)
+
+
+def binary_eval_raw(scores, labels, high_flags) -> torch.Tensor:
+    """qst_binary_eval on contiguous fp32 HIP scores [nsets, n], contiguous int64 HIP labels [n] in {0, 1} and one flag per
+    set (true: a higher score is more similar): float64 [nsets, 8] on the device, per set {accuracy, accuracy_threshold, f1,
+    precision, recall, f1_threshold, ap, number of positives}. No host synchronisation."""
+    lib = _lib.load()
+    nsets, n = scores.shape
+    high_flags = list(high_flags)
+    if nsets < 1 or n < 1 or len(high_flags) != nsets or labels.numel() != n:
+        raise ValueError(f"binary_eval: scores {tuple(scores.shape)} need at least one row and one pair, {nsets} flags and "
+                         f"{n} labels; {len(high_flags)} flags and {labels.numel()} labels given")
+    flags = (_lib.C.c_int32 * nsets)(*[int(bool(f)) for f in high_flags])
+    if n > BINARY_EVAL_MAX_PAIRS or nsets > BINARY_EVAL_MAX_SETS:
+        raise _lib.QstError(f"binary_eval: {n} pairs in {nsets} score rows; the kernel takes up to {BINARY_EVAL_MAX_PAIRS} "
+                            f"(2^20) pairs and {BINARY_EVAL_MAX_SETS} rows")
+    out = torch.empty(nsets, 8, dtype=torch.float64, device=scores.device)
+    nbytes = int(lib.qst_binary_eval_workspace_bytes(n, nsets))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=scores.device)
+    with torch.cuda.device(scores.device):
+        _lib.check(lib.qst_binary_eval(scores.data_ptr(), labels.data_ptr(), n, nsets, flags, out.data_ptr(), ws.data_ptr(),
+                                       nbytes, _lib.current_stream_ptr()), "qst_binary_eval")
+    return out
+
+
 class _SoftmaxHeadFn(torch.autograd.Function):
     """logits = classifier([u, v, |u - v|, u * v]): qst_softmax_head_fwd, and qst_softmax_head_bwd from autograd's dlogits."""
 
