@@ -1214,15 +1214,27 @@ extern "C" int qst_encoder_backward(qst_encoder* e, const int64_t* ids, const in
                                         saved_bytes, workspace, workspace_bytes, 1, e->cfg.num_layers, 0, 1, stream);
 }
 
+// The arena group and the hyper-parameters every optimiser entry point takes; each entry adds its own fields (optim.hip).
+static AdamStep adam_step(const qst_encoder* e, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, float max_grad_norm, float grad_scale,
+                          float* norm_out, float* scratch) {
+    AdamStep s = {};
+    s.arena = {params, grads, exp_avg, exp_avg_sq, e->chunk_decay, e->lay.total};
+    s.lr = lr; s.beta1 = beta1; s.beta2 = beta2; s.eps = eps; s.wd = weight_decay; s.max_norm = max_grad_norm;
+    s.grad_scale = grad_scale; s.norm_out = norm_out; s.scratch = scratch;
+    return s;
+}
+
 extern "C" int qst_clip_adamw_step_sched(const qst_encoder* e, float* params, float* grads, float* exp_avg,
                                          float* exp_avg_sq, float base_lr, float beta1, float beta2, float eps,
                                          float weight_decay, float max_grad_norm, float grad_scale,
                                          int64_t warmup_steps, int64_t total_steps, int64_t* step_dev,
                                          float* norm_out, float* scratch, void* stream) {
     if (!e) return QST_ERR_BAD_ARG;
-    return qst_adamw_launch_sched(params, grads, exp_avg, exp_avg_sq, e->chunk_decay, e->lay.total, base_lr, beta1, beta2,
-                                  eps, weight_decay, max_grad_norm, grad_scale, warmup_steps, total_steps, step_dev,
-                                  norm_out, scratch, (hipStream_t)stream);
+    AdamStep s = adam_step(e, params, grads, exp_avg, exp_avg_sq, base_lr, beta1, beta2, eps, weight_decay, max_grad_norm,
+                           grad_scale, norm_out, scratch);
+    s.step_dev = step_dev; s.warmup = warmup_steps; s.total = total_steps;
+    return qst_adamw_run(s, (hipStream_t)stream);
 }
 
 extern "C" int qst_clip_adamw_step_amp(const qst_encoder* e, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
@@ -1230,10 +1242,12 @@ extern "C" int qst_clip_adamw_step_amp(const qst_encoder* e, float* params, floa
                                        float max_grad_norm, float grad_scale, int64_t warmup_steps, int64_t total_steps,
                                        int64_t* step_dev, float* scaler_dev, float growth_factor, float backoff_factor,
                                        int32_t growth_interval, float* norm_out, float* scratch, void* stream) {
-    if (!e) return QST_ERR_BAD_ARG;
-    return qst_adamw_launch_amp(params, grads, exp_avg, exp_avg_sq, e->chunk_decay, e->lay.total, base_lr, beta1, beta2, eps,
-                                weight_decay, max_grad_norm, grad_scale, warmup_steps, total_steps, step_dev, scaler_dev,
-                                growth_factor, backoff_factor, growth_interval, norm_out, scratch, (hipStream_t)stream);
+    if (!e || !scaler_dev) return QST_ERR_BAD_ARG;          // (without a scaler the descriptor would be the _sched step)
+    AdamStep s = adam_step(e, params, grads, exp_avg, exp_avg_sq, base_lr, beta1, beta2, eps, weight_decay, max_grad_norm,
+                           grad_scale, norm_out, scratch);
+    s.step_dev = step_dev; s.warmup = warmup_steps; s.total = total_steps;
+    s.scaler = scaler_dev; s.growth = growth_factor; s.backoff = backoff_factor; s.interval = growth_interval;
+    return qst_adamw_run(s, (hipStream_t)stream);
 }
 
 extern "C" int qst_clip_adamw_step(const qst_encoder* e, float* params, float* grads, float* exp_avg,
@@ -1241,8 +1255,10 @@ extern "C" int qst_clip_adamw_step(const qst_encoder* e, float* params, float* g
                                    float weight_decay, float max_grad_norm, float grad_scale, int64_t step,
                                    float* norm_out, float* scratch, void* stream) {
     if (!e) return QST_ERR_BAD_ARG;
-    return qst_adamw_launch(params, grads, exp_avg, exp_avg_sq, e->chunk_decay, e->lay.total, lr, beta1, beta2, eps,
-                            weight_decay, max_grad_norm, grad_scale, step, norm_out, scratch, (hipStream_t)stream);
+    AdamStep s = adam_step(e, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, max_grad_norm,
+                           grad_scale, norm_out, scratch);
+    s.step = step;
+    return qst_adamw_run(s, (hipStream_t)stream);
 }
 
 extern "C" int qst_clip_adamw_step_joint(const qst_encoder* e, float* params, float* grads, float* exp_avg,
@@ -1251,9 +1267,11 @@ extern "C" int qst_clip_adamw_step_joint(const qst_encoder* e, float* params, fl
                                          float beta1, float beta2, float eps, float weight_decay, float max_grad_norm,
                                          float grad_scale, int64_t step, float* norm_out, float* scratch, void* stream) {
     if (!e) return QST_ERR_BAD_ARG;
-    return qst_adamw_launch_joint(params, grads, exp_avg, exp_avg_sq, e->chunk_decay, e->lay.total, x_params, x_grads,
-                                  x_exp_avg, x_exp_avg_sq, x_chunk_decay, x_n, lr, beta1, beta2, eps, weight_decay,
-                                  max_grad_norm, grad_scale, step, norm_out, scratch, (hipStream_t)stream);
+    AdamStep s = adam_step(e, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, max_grad_norm,
+                           grad_scale, norm_out, scratch);
+    s.extra = {x_params, x_grads, x_exp_avg, x_exp_avg_sq, x_chunk_decay, x_n};
+    s.step = step;
+    return qst_adamw_run(s, (hipStream_t)stream);
 }
 
 extern "C" int64_t qst_abi_sizeof(int which) {

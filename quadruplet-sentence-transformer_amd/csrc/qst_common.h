@@ -40,28 +40,17 @@ typedef __attribute__((ext_vector_type(8))) op16 op16x8;
 
 extern "C" int qst_set_hip_error(int code);
 
-// AdamW steps (optim.hip) behind the qst_clip_adamw_step* entry points of qst_api.hip
-extern "C" int qst_adamw_launch(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
-                                const uint8_t* chunk_decay, int64_t n, float lr, float beta1, float beta2, float eps,
-                                float weight_decay, float max_grad_norm, float grad_scale, int64_t step,
-                                float* norm_out, float* scratch, hipStream_t st);
-extern "C" int qst_adamw_launch_joint(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
-                                      const uint8_t* chunk_decay, int64_t n, float* x_params, float* x_grads,
-                                      float* x_exp_avg, float* x_exp_avg_sq, const uint8_t* x_chunk_decay, int64_t x_n,
-                                      float lr, float beta1, float beta2, float eps, float weight_decay,
-                                      float max_grad_norm, float grad_scale, int64_t step, float* norm_out, float* scratch,
-                                      hipStream_t st);
-extern "C" int qst_adamw_launch_sched(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
-                                      const uint8_t* chunk_decay, int64_t n, float base_lr, float beta1, float beta2,
-                                      float eps, float weight_decay, float max_grad_norm, float grad_scale,
-                                      int64_t warmup_steps, int64_t total_steps, int64_t* step_dev, float* norm_out,
-                                      float* scratch, hipStream_t st);
-extern "C" int qst_adamw_launch_amp(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
-                                    const uint8_t* chunk_decay, int64_t n, float base_lr, float beta1, float beta2,
-                                    float eps, float weight_decay, float max_grad_norm, float grad_scale,
-                                    int64_t warmup_steps, int64_t total_steps, int64_t* step_dev, float* scaler_dev,
-                                    float growth, float backoff, int growth_interval, float* norm_out, float* scratch,
-                                    hipStream_t st);
+// The AdamW step (optim.hip) behind the qst_clip_adamw_step* entry points of qst_api.hip: what is filled in selects the form.
+struct AdamGroup { float *p, *g, *m, *v; const uint8_t* chunk_decay; int64_t n; };   // n % 256 == 0, a decay flag per 256
+struct AdamStep {
+    AdamGroup arena, extra;                                 // extra.n == 0: no second group
+    float lr, beta1, beta2, eps, wd, max_norm, grad_scale;  // lr: the base rate under the device schedule
+    int64_t step;                                           // the host's 1-based step (used without a device counter)
+    int64_t* step_dev; int64_t warmup, total;               // device schedule when step_dev != null ([2] with a scaler)
+    float* scaler; float growth, backoff; int interval;     // GradScaler's rules when scaler != null (needs step_dev)
+    float* norm_out; float* scratch;                        // scratch: 2048 floats
+};
+int qst_adamw_run(const AdamStep& s, hipStream_t st);
 
 #define QST_HIP_CHECK(expr)                                 \
     do {                                                    \

@@ -358,22 +358,18 @@ class HipEncoder:
             self._clip_adamw("qst_clip_adamw_step", lr, betas, eps, weight_decay, max_grad_norm, grad_scale, self.opt_step)
             return
         extra.ensure_state()
-        self.ensure_train_state()
-        _lib.check(self.lib.qst_clip_adamw_step_joint(
-            self.handle, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-            extra.params.data_ptr(), extra.grads.data_ptr(), extra.exp_avg.data_ptr(), extra.exp_avg_sq.data_ptr(),
-            extra.chunk_decay.data_ptr(), extra.total, lr, betas[0], betas[1], eps, weight_decay, max_grad_norm, grad_scale,
-            self.opt_step, self.grad_norm.data_ptr(), self._scratch.data_ptr(), _lib.current_stream_ptr()),
-            "qst_clip_adamw_step_joint")
-        self.mark_stale()
+        self._clip_adamw("qst_clip_adamw_step_joint", lr, betas, eps, weight_decay, max_grad_norm, grad_scale, self.opt_step,
+                         front=(extra.params.data_ptr(), extra.grads.data_ptr(), extra.exp_avg.data_ptr(),
+                                extra.exp_avg_sq.data_ptr(), extra.chunk_decay.data_ptr(), extra.total))
 
-    def _clip_adamw(self, entry: str, lr, betas, eps, weight_decay, max_grad_norm, grad_scale, *extra) -> None:
-        """What the three optimiser steps share: the arenas and AdamW arguments in front of an entry point's own (`extra`),
-        the norm and scratch behind them, and every shadow stale afterwards."""
+    def _clip_adamw(self, entry: str, lr, betas, eps, weight_decay, max_grad_norm, grad_scale, *own, front=()) -> None:
+        """What the four optimiser steps share: the arenas, then what an entry point takes in front of the AdamW arguments
+        (`front`: the joint step's extra group), those arguments, the entry point's own (`own`), the norm and scratch
+        behind them, and every shadow stale afterwards."""
         self.ensure_train_state()
         _lib.check(getattr(self.lib, entry)(
             self.handle, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
-            self.exp_avg_sq.data_ptr(), lr, betas[0], betas[1], eps, weight_decay, max_grad_norm, grad_scale, *extra,
+            self.exp_avg_sq.data_ptr(), *front, lr, betas[0], betas[1], eps, weight_decay, max_grad_norm, grad_scale, *own,
             self.grad_norm.data_ptr(), self._scratch.data_ptr(), _lib.current_stream_ptr()), entry)
         self.mark_stale()
 

@@ -493,14 +493,15 @@ class SentenceTransformer(nn.Module):
             world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
         dp_mode = (data_parallel or "split_batch") if world > 1 else "off"
         # a loss that owns parameters outside the arena (owned_parameters() -> loss_params.LossParameters: SoftmaxLoss's
-        # classifier) is clipped and stepped with the encoder by enc.adamw_step(extra=...); what has no joint form refuses here
+        # classifier) is clipped and stepped with the encoder by enc.adamw_step(extra=...); what has no joint entry point refuses here
         owned = [lm.owned_parameters() if hasattr(lm, "owned_parameters") else None for lm in loss_models]
         for lm, op in zip(loss_models, owned):
             if op is None:
                 continue
             why = None
             if amp:
-                why = f"precision={precision!r} / use_amp: the mixed-precision optimiser step has no joint form yet"
+                why = (f"precision={precision!r} / use_amp: optim.hip's step takes an extra group together with the loss "
+                       f"scaler, but no entry point passes both and no test covers it yet")
             elif world > 1:
                 why = f"a data-parallel world of {world}: the loss's own gradients are not exchanged between the ranks"
             elif resume_from_checkpoint is not None:
