@@ -469,6 +469,34 @@ int qst_softmax_ce(const float* logits, const int64_t* labels, int B, int C, int
                    float* out_loss, const float* grad_out, float* dlogits, int64_t* counts, float* scratch, void* stream);
 
 /*
+ * sentence-transformers 2.2.2's models.Dense on pooled sentence embeddings, with the models.Normalize that may follow it
+ * (version 110; csrc/dense_head.hip):
+ *   z = x W^T + b;  a = act(z);  y = a, or a / max(|a|_2, 1e-12) per row with `normalize` (F.normalize, eps 1e-12)
+ * All fp32, no atomics, every sum in a fixed order (the same inputs give the same bits), on the caller's stream without host
+ * synchronisation; the products run on the LDS-tiled fp32 FMA loop of the batch losses, every edge guarded.
+ *   x        : f32 [B, Din] with row stride ldx >= Din (a column block of a wider buffer is fine)
+ *   w        : f32 [Dout, Din], torch.nn.Linear layout; b f32 [Dout] or NULL = no bias
+ *   act      : QST_DENSE_ACT_*; normalize: 0 or 1
+ *   y        : f32 [B, Dout]; row_norm f32 [B] = |a| of every row, written with normalize only (may be NULL without)
+ * B >= 1 (up to 2^29), 1 <= Din, Dout <= 8192, no multiple-of-anything requirement: anything else QST_ERR_UNSUPPORTED. A NULL
+ * required pointer, ldx < Din, another act, a normalize other than 0 or 1, a workspace that is too small or not 16-byte
+ * aligned: QST_ERR_BAD_ARG. Both before any launch, nothing written.
+ */
+enum { QST_DENSE_ACT_IDENTITY = 0, QST_DENSE_ACT_TANH = 1 };
+int qst_dense_head_fwd(const float* x, int ldx, const float* w, const float* b, int B, int Din, int Dout, int act,
+                       int normalize, float* y, float* row_norm, void* stream);
+/* From dy f32 [B, Dout], the forward's y and (with normalize) row_norm: grad_x f32 [B, Din], grad_w f32 [Dout, Din] and
+ * grad_b f32 [Dout] (NULL = skipped), all written (not accumulated). Through the normalisation da = (dy - y <y, dy>) /
+ * max(|a|, 1e-12) -- a row with |a| < 1e-12 gets dy / 1e-12, as torch's clamp does -- and through tanh dz = da (1 - a^2)
+ * with a = y * max(|a|, 1e-12): nothing but y and row_norm is kept from the forward. The weight and bias gradients walk the
+ * rows in order, in up to 16 slices of at least 64 rows whose partial sums are added in the order of the slices. workspace:
+ * qst_dense_head_bwd_workspace_bytes (dz and the partial sums; 0 for sizes outside the limits), always required. */
+size_t qst_dense_head_bwd_workspace_bytes(int B, int Din, int Dout);
+int qst_dense_head_bwd(const float* x, int ldx, const float* w, const float* y, const float* row_norm, const float* dy,
+                       int B, int Din, int Dout, int act, int normalize, float* grad_x, float* grad_w, float* grad_b,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * What sentence-transformers 2.2.2's evaluation.BinaryClassificationEvaluator computes from the scores of n sentence pairs
  * and their labels in {0, 1} (version 109; csrc/binary_eval.hip), for nsets score rows over the same labels in one call.
  * With `rows` the stable sort of (score, label) by score -- descending where high_is_similar[set] != 0 (cosine, dot),

@@ -113,6 +113,10 @@ SIGNATURES = {
     "qst_softmax_head_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "qst_softmax_head_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "qst_softmax_head_bwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "qst_dense_head_fwd": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "qst_dense_head_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "qst_dense_head_bwd": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,
+                                     C.c_size_t, vp]),
     "qst_softmax_ce": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp]),
     "qst_binary_eval_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "qst_binary_eval": (C.c_int, [vp, vp, C.c_int64, C.c_int, c_i32p, vp, vp, C.c_size_t, vp]),

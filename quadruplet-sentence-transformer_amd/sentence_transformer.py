@@ -31,7 +31,8 @@ from torch import nn
 from . import _lib
 from .config import ARCH_BERT, ARCH_MPNET, ARCH_ROBERTA, PRESETS, EncoderConfig, hf_param_views
 from .encoder import HipEncoder
-from .models import Normalize, Pooling, Transformer, pooling_from_config
+from .loss_params import LossParameters
+from .models import Dense, Normalize, Pooling, Transformer, pooling_from_config
 from .synthetic import synthetic_params
 from .trainer import allreduce_ranges, gradient_buckets, staged_backward, staged_reduce_order, warmup_linear_lr
 
@@ -194,13 +195,16 @@ class SentenceTransformer(nn.Module):
         arena = None
         tok_dir = None
         self._dropout_config = (0.1, 0.1)        # HF defaults; a loaded config.json overrides (fit(dropout="config"))
+        dense, dense_normalize = None, False     # a models.Dense after pooling, and whether a Normalize follows it
         if modules is not None:
-            # models.Transformer -> models.Pooling -> [models.Normalize]: the one chain the library runs
+            # models.Transformer -> models.Pooling -> [models.Dense] -> [models.Normalize]: the chains the library runs
             cfg, arena, tok_dir, self._dropout_config = _load_module_chain(modules, cache_folder)
+            dense, dense_normalize = _module_chain_dense(modules, cfg)
         elif config is not None:
             cfg = config
         elif model_name_or_path is not None and os.path.isdir(str(model_name_or_path)):
             cfg, arena, tok_dir = _load_model_dir(str(model_name_or_path))
+            dense, dense_normalize = _load_dense_head(str(model_name_or_path), cfg)
             self._dropout_config = _dropout_from_config(str(model_name_or_path))
         else:
             full = str(model_name_or_path or "all-MiniLM-L6-v2")
@@ -208,6 +212,7 @@ class SentenceTransformer(nn.Module):
             found = _find_cached_model(full, cache_folder)
             if found is not None:
                 cfg, arena, tok_dir = _load_model_dir(found)
+                dense, dense_normalize = _load_dense_head(found, cfg)
                 self._dropout_config = _dropout_from_config(found)
             else:
                 if name not in PRESETS:
@@ -250,6 +255,14 @@ class SentenceTransformer(nn.Module):
         self._dp_works, self._dp_reduced = [], False
         self._anchor = nn.Parameter(torch.zeros((), device=dev))      # makes the Function's output require grad
         self._build_named_parameters()
+        # the Dense head is module "2" (named_parameters(): 2.linear.weight, 2.linear.bias), its parameters rehomed into a flat
+        # buffer that the joint optimiser step takes next to the arena. The ENCODER's cfg.normalize is False under a Dense:
+        # whether the model normalises is applied after the Dense, by the head kernel
+        self._dense_normalize = bool(dense_normalize) and dense is not None
+        self._dense_params = None
+        if dense is not None:
+            self.add_module("2", dense)
+            self._dense_params = LossParameters(dense, device=dev)
         self.best_score = -9999999
 
     # ---- parameters as views of the arena
@@ -284,8 +297,13 @@ class SentenceTransformer(nn.Module):
             raise _lib.QstError(f"this model lives on {self._target_device}; moving the arena to {dev} is not supported")
         return self
 
+    @property
+    def _dense(self) -> Optional[Dense]:
+        return self._modules.get("2")
+
     def get_sentence_embedding_dimension(self) -> int:
-        return self.cfg.embedding_dim
+        dense = self._dense
+        return self.cfg.embedding_dim if dense is None else dense.get_sentence_embedding_dimension()
 
     def get_max_seq_length(self) -> int:
         return self.max_seq_length
@@ -333,6 +351,10 @@ class SentenceTransformer(nn.Module):
         training = (1 if torch.is_grad_enabled() else (2 if self._enc.dropout is not None else 0)) if self.training else 0
         with torch.cuda.device(dev):
             emb = _EncodeFn.apply(self._anchor, self, ids, mask, types, training)
+            dense = self._dense
+            if dense is not None:                       # models.Dense [+ models.Normalize] on the pooled embedding
+                self._dense_params.ensure()
+                emb = dense.project(emb, self._dense_normalize)
         features.update({"sentence_embedding": emb})
         return features
 
@@ -369,7 +391,7 @@ class SentenceTransformer(nn.Module):
                     _lib.check(self._enc.lib.qst_normalize_rows(emb.data_ptr(), emb.shape[0], emb.shape[1], emb.data_ptr(),
                                                                 _lib.current_stream_ptr()), "qst_normalize_rows")
                 chunks.append(emb.cpu() if convert_to_numpy else emb)
-        allemb = torch.cat(chunks, 0) if chunks else torch.zeros(0, self.cfg.embedding_dim)
+        allemb = torch.cat(chunks, 0) if chunks else torch.zeros(0, self.get_sentence_embedding_dimension())
         inv = np.argsort(order)
         allemb = allemb[torch.as_tensor(inv, device=allemb.device)] if len(inv) else allemb
         if convert_to_numpy:
@@ -495,6 +517,24 @@ class SentenceTransformer(nn.Module):
         # a loss that owns parameters outside the arena (owned_parameters() -> loss_params.LossParameters: SoftmaxLoss's
         # classifier) is clipped and stepped with the encoder by enc.adamw_step(extra=...); what has no joint entry point refuses here
         owned = [lm.owned_parameters() if hasattr(lm, "owned_parameters") else None for lm in loss_models]
+        # the model's own Dense head is such a group too, and the joint entry point takes ONE extra group
+        dense_params = self._dense_params
+        if dense_params is not None:
+            why = None
+            if any(op is not None for op in owned):
+                names = sorted({type(lm).__name__ for lm, op in zip(loss_models, owned) if op is not None})
+                why = (f"{', '.join(names)}, a loss that trains parameters of its own: the joint optimiser step takes one "
+                       f"group of parameters next to the encoder's, and the Dense head is that group")
+            elif amp:
+                why = (f"precision={precision!r} / use_amp: no entry point passes an extra parameter group together with the "
+                       f"loss scaler")
+            elif world > 1:
+                why = f"a data-parallel world of {world}: the Dense head's gradients are not exchanged between the ranks"
+            elif resume_from_checkpoint is not None:
+                why = "resume_from_checkpoint: checkpoints hold the Dense head's weights but not its Adam moments"
+            if why is not None:
+                raise NotImplementedError(f"fit(): this model has a models.Dense head, which is not supported with {why}")
+            dense_params.ensure().zero_grad()
         for lm, op in zip(loss_models, owned):
             if op is None:
                 continue
@@ -585,7 +625,7 @@ class SentenceTransformer(nn.Module):
                                                weight_decay, float(max_grad_norm), 1.0 / world)
                         else:
                             enc.adamw_step(lr_at(global_step), betas, eps, weight_decay, float(max_grad_norm), 1.0 / world,
-                                           extra=owned[idx])
+                                           extra=owned[idx] if owned[idx] is not None else dense_params)
                     training_steps += 1
                     global_step += 1
                     if evaluation_steps > 0 and training_steps % evaluation_steps == 0:
@@ -667,6 +707,10 @@ class SentenceTransformer(nn.Module):
         if (cfg.pooling, cfg.normalize) != (self.cfg.pooling, self.cfg.normalize):
             raise ValueError(f"{path}: checkpoint head (pooling {cfg.pooling!r}, normalize {cfg.normalize}) differs from this "
                              f"model's (pooling {self.cfg.pooling!r}, normalize {self.cfg.normalize})")
+        ck_dense, ck_normalize = _load_dense_head(path, cfg)
+        mine, theirs = _dense_signature(self._dense, self._dense_normalize), _dense_signature(ck_dense, ck_normalize)
+        if mine != theirs:
+            raise ValueError(f"{path}: checkpoint Dense head ({theirs or 'none'}) differs from this model's ({mine or 'none'})")
         self._enc.load_arena(arena)
         st = load_file(state_file)
         st["opt_step"] = torch.tensor([int(meta["opt_step"])], dtype=torch.int64)
@@ -703,7 +747,14 @@ class SentenceTransformer(nn.Module):
         if cfg.pooling != "mean":                          # (the mean head's file stays what it always was)
             pool = Pooling(cfg.hidden_size, pooling_mode=cfg.pooling).get_config_dict()
         json.dump(pool, open(os.path.join(path, "1_Pooling", "config.json"), "w"), indent=2)
-        if cfg.normalize:
+        dense = self._dense
+        if dense is not None:
+            modules.append({"idx": 2, "name": "2", "path": "2_Dense", "type": "sentence_transformers.models.Dense"})
+            dense.save(os.path.join(path, "2_Dense"))
+            if self._dense_normalize:
+                modules.append({"idx": 3, "name": "3", "path": "3_Normalize", "type": "sentence_transformers.models.Normalize"})
+                os.makedirs(os.path.join(path, "3_Normalize"), exist_ok=True)
+        elif cfg.normalize:
             modules.append({"idx": 2, "name": "2", "path": "2_Normalize", "type": "sentence_transformers.models.Normalize"})
             os.makedirs(os.path.join(path, "2_Normalize"), exist_ok=True)
         json.dump(modules, open(os.path.join(path, "modules.json"), "w"), indent=2)
@@ -799,15 +850,80 @@ def _find_cached_model(name: str, cache_folder: Optional[str] = None) -> Optiona
     return None
 
 
+def _dense_chain_problem(kinds: List[str]) -> Optional[str]:
+    """What is wrong with where models.Dense stands in a chain of module class names (None: nothing, or no Dense at all).
+    The head kernel runs one Dense, after pooling, with the normalisation behind it."""
+    if "Dense" not in kinds:
+        return None
+    if kinds.count("Dense") > 1:
+        return f"{kinds.count('Dense')} Dense modules: exactly one Dense after Pooling is supported"
+    before = kinds[:kinds.index("Dense")]
+    if "Pooling" not in before:
+        return "Dense before Pooling: the Dense head runs on the pooled sentence embedding, not on token embeddings"
+    if "Normalize" in before:
+        return "Dense after Normalize: the normalisation is applied behind the Dense head, not in front of it"
+    return None
+
+
+def _dense_signature(dense: Optional[Dense], normalize: bool):
+    """What two Dense heads must share to be the same head: the config and whether a Normalize follows. None: no Dense."""
+    return None if dense is None else dict(dense.get_config_dict(), normalize=bool(normalize))
+
+
+def _check_dense_width(dense: Dense, cfg: EncoderConfig, where: str) -> None:
+    if dense.in_features != cfg.embedding_dim:
+        raise NotImplementedError(f"{where}: models.Dense in_features {dense.in_features} differs from the pooled width "
+                                  f"{cfg.embedding_dim} (pooling {cfg.pooling!r} of hidden_size {cfg.hidden_size})")
+
+
+def _module_chain_dense(modules, cfg: EncoderConfig):
+    """(the models.Dense of a module list _load_module_chain accepted or None, whether a Normalize follows it)."""
+    mods = list(modules.values()) if isinstance(modules, (dict, OrderedDict)) else list(modules)
+    dense = next((m for m in mods if isinstance(m, Dense)), None)
+    if dense is None:
+        return None, False
+    _check_dense_width(dense, cfg, "SentenceTransformer(modules=...)")
+    return dense, any(isinstance(m, Normalize) for m in mods)
+
+
+def _load_dense_head(path: str, cfg: EncoderConfig):
+    """(the models.Dense a model directory's modules.json names or None, whether a Normalize follows it). `cfg`: what
+    _load_model_dir returned for the directory. The Dense's own directory is its entry's `path` (2_Dense by convention)."""
+    mj = os.path.join(path, "modules.json")
+    if not os.path.exists(mj):
+        return None, False
+    mods = json.load(open(mj))
+    kinds = [m.get("type", "").rsplit(".", 1)[-1] for m in mods]
+    if "Dense" not in kinds:
+        return None, False
+    problem = _dense_chain_problem(kinds)
+    if problem is not None:
+        raise NotImplementedError(f"{path}: {problem}")
+    entry = mods[kinds.index("Dense")]
+    try:
+        dense = Dense.load(os.path.join(path, entry.get("path", "2_Dense")))
+    except NotImplementedError as e:
+        raise NotImplementedError(f"{path}: {e}") from None
+    _check_dense_width(dense, cfg, path)
+    return dense, "Normalize" in kinds
+
+
 def _load_module_chain(modules, cache_folder: Optional[str] = None):
-    """SentenceTransformer(modules=[models.Transformer, models.Pooling, models.Normalize (optional)]): (cfg, arena,
-    tokenizer dir, dropout config) of the Transformer's checkpoint with the head the Pooling / Normalize descriptors name.
-    Any other module list is refused."""
+    """SentenceTransformer(modules=[models.Transformer, models.Pooling, models.Dense (optional), models.Normalize
+    (optional)]): (cfg, arena, tokenizer dir, dropout config) of the Transformer's checkpoint with the head the Pooling /
+    Normalize descriptors name. Any other module list is refused. With a Dense the encoder itself does not normalise
+    (cfg.normalize is False): _module_chain_dense says what follows the encoder."""
     mods = list(modules.values()) if isinstance(modules, (dict, OrderedDict)) else list(modules)
     kinds = [type(m) for m in mods]
-    if kinds not in ([Transformer, Pooling], [Transformer, Pooling, Normalize]):
+    problem = _dense_chain_problem([k.__name__ for k in kinds])
+    if problem is not None:
+        raise NotImplementedError(f"custom module lists are outside the hot path this build covers: {problem}; got "
+                                  f"{[k.__name__ for k in kinds]}")
+    if kinds not in ([Transformer, Pooling], [Transformer, Pooling, Normalize], [Transformer, Pooling, Dense],
+                     [Transformer, Pooling, Dense, Normalize]):
         raise NotImplementedError("custom module lists are outside the hot path this build covers: only "
-                                  "[models.Transformer, models.Pooling] and [..., models.Normalize] are accepted, got "
+                                  "[models.Transformer, models.Pooling], [..., models.Normalize], [..., models.Dense] and "
+                                  "[..., models.Dense, models.Normalize] are accepted, got "
                                   f"{[k.__name__ for k in kinds]}")
     tr, pool = mods[0], mods[1]
     path = str(tr.model_name_or_path)
@@ -821,7 +937,7 @@ def _load_module_chain(modules, cache_folder: Optional[str] = None):
         raise NotImplementedError(f"models.Pooling({pool.word_embedding_dimension}, ...): word_embedding_dimension differs "
                                   f"from the checkpoint's hidden_size {cfg.hidden_size}")
     max_seq = cfg.max_seq_length if tr.max_seq_length is None else min(512, int(tr.max_seq_length))
-    cfg = replace(cfg, pooling=pool.pooling, normalize=len(mods) == 3, max_seq_length=max_seq)
+    cfg = replace(cfg, pooling=pool.pooling, normalize=Normalize in kinds and Dense not in kinds, max_seq_length=max_seq)
     return cfg, arena, tok_dir, _dropout_from_config(path)
 
 
@@ -860,12 +976,17 @@ def _load_model_dir_sd(path: str):
     mj = os.path.join(path, "modules.json")
     if os.path.exists(mj):
         mods = json.load(open(mj))
-        normalize = any(m.get("type", "").endswith("Normalize") for m in mods)
+        kinds = [m.get("type", "").rsplit(".", 1)[-1] for m in mods]
+        problem = _dense_chain_problem(kinds)
+        if problem is not None:
+            raise NotImplementedError(f"{path}: {problem}")
+        # under a Dense (read by _load_dense_head) the normalisation follows the Dense, not the encoder
+        normalize = "Normalize" in kinds and "Dense" not in kinds
         for m in mods:
             kind = m.get("type", "").rsplit(".", 1)[-1]
-            if kind not in ("Transformer", "Pooling", "Normalize"):
+            if kind not in ("Transformer", "Pooling", "Dense", "Normalize"):
                 raise NotImplementedError(f"{path}: module '{m.get('type')}' is not on the accelerated path "
-                                          "(Transformer -> Pooling -> [Normalize])")
+                                          "(Transformer -> Pooling -> [Dense] -> [Normalize])")
             if kind == "Pooling":
                 pc = os.path.join(path, m.get("path", "1_Pooling"), "config.json")
                 if os.path.exists(pc):

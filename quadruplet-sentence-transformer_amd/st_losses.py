@@ -767,8 +767,9 @@ class BatchAllTripletLoss(_BatchTripletLoss):
 # ------------------------------------------------------------------ distillation from a teacher
 class MSELoss(_TupleLoss):
     """nn.MSELoss() between the student's embedding of the one text column and `labels`, the teacher's embedding of each
-    example [B, D]: one qst_embed_mse call. The teacher and the student must have the same embedding width (sentence-
-    transformers users put a Dense or PCA layer in between otherwise; that is not done here)."""
+    example [B, D]: one qst_embed_mse call. The teacher and the student must have the same embedding width; where they
+    differ, the model carries a models.Dense behind its pooling (a trained projection, or the teacher's PCA), as
+    sentence-transformers users do."""
     reduction = "mean"
 
     def __init__(self, model):
