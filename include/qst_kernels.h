@@ -417,6 +417,45 @@ int qst_topk_stream(const float* queries, const float* corpus, int nq, int nc, i
                     int64_t query_base, int64_t corpus_base, int exclude_self, float max_score,
                     float* run_scores, int64_t* run_index, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Community detection (sentence-transformers 2.2.2 util.community_detection) without the n x n matrix. With S the cosine
+ * scores of the rows of emb f32 [n, dim] among themselves -- prepared and multiplied exactly as qst_score_matrix and
+ * qst_topk_stream do it (rows normalised with eps 1e-12, the split-bf16 x3 GEMM) -- and N(i) = { j : S[i, j] >= threshold }
+ * (the row itself when its own score passes; a NaN score passes nothing):
+ *   qst_community_count    counts[i] = |N(i)|, int32 [n]; self_member (nullable, uint8 [n]) = 1 where i is in N(i).
+ *   qst_community_members  the members of N(row0 + r) for the rows r of ONE row block, row0 % 2048 == 0 and
+ *                          0 <= row0 < n (else QST_ERR_BAD_ARG), min(2048, n - row0) rows. begin int64 / capacity int32 /
+ *                          written int32 are indexed by r. A row with begin[r] < 0 is skipped; any other gets its members
+ *                          in ascending column order at out_index (int32) / out_score (f32, the scores that qualified
+ *                          them) [begin[r] ...]. Nothing is stored at or past begin[r] + capacity[r]; written[r] (zeroed
+ *                          for the whole block first) still receives the number that qualified, so a capacity that is
+ *                          too small shows and corrupts nothing. Deterministic: ballot + popcount prefix, no atomics.
+ *   Both walk the same [2048-row block] x [chunk] score panels through the same call, so a score has the same bits in
+ *   both and written[r] == counts[row0 + r]; the member pass does NOT score a gathered set of rows (the GEMM's result
+ *   must not be made to depend on how rows are grouped). Columns added to pad a panel to 4 are never looked at.
+ *   The workspace (qst_community_workspace_bytes: linear in n at a fixed chunk) holds the prepared rows and one
+ *   [min(n, 2048), chunk rounded up to 4] panel; a chunk's operand is a slice of the prepared rows. chunk > n is n.
+ *   dim % 32 == 0 and one chunk's operand below 2^31 bytes, else QST_ERR_UNSUPPORTED; a NULL pointer, a non-positive
+ *   size or a NaN threshold: QST_ERR_BAD_ARG before any launch; a short workspace: QST_ERR_WORKSPACE.
+ *   qst_community_claim    the greedy pass over ncand candidates IN THE GIVEN ORDER: candidate c owns
+ *                          members[begin[c] .. begin[c] + len[c]) (int32 row numbers); it is accepted (accepted[c] = 1,
+ *                          else 0) when none of them is set in taken uint8 [n], and then sets them all. A candidate
+ *                          with no members, a negative begin or a member outside [0, n) is rejected. One workgroup,
+ *                          a barrier between candidates. taken persists between calls; ncand == 0 launches nothing.
+ *   qst_community_rescore  out[p] (f64) = the cosine of rows rows_a[p] and rows_b[p] of emb, summed in fp64 from the
+ *                          rows as given (norms clamped at 1e-12), p < count; NaN for a row outside [0, n). Pairs that
+ *                          are equally similar get equal values, which the x3 scores do not promise in their last
+ *                          bits: the order INSIDE an accepted community is taken from these. count == 0 is a no-op. */
+size_t qst_community_workspace_bytes(int n, int chunk, int dim);
+int qst_community_count(const float* emb, int n, int dim, float threshold, int chunk, int32_t* counts,
+                        uint8_t* self_member, void* workspace, size_t workspace_bytes, void* stream);
+int qst_community_members(const float* emb, int n, int dim, float threshold, int chunk, int row0, const int64_t* begin,
+                          const int32_t* capacity, int32_t* out_index, float* out_score, int32_t* written,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int qst_community_claim(const int64_t* begin, const int32_t* len, int ncand, const int32_t* members, int n,
+                        uint8_t* taken, uint8_t* accepted, void* stream);
+int qst_community_rescore(const float* emb, int n, int dim, const int32_t* rows_a, const int32_t* rows_b, int64_t count,
+                          double* out, void* stream);
+
 /* All GEMM weights of the arena in one launch; table_dev = int64 [nseg][6] {src off, rows, cols, dst off, dstT off,
  * first block} (built by qst_encoder_create). */
 int qst_shadow_all(const float* params, void* shadow, const int64_t* table_dev, int nseg, int nblocks, void* stream);

@@ -218,6 +218,12 @@ SIGNATURES = {
     "qst_topk_stream_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "qst_topk_stream": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                   C.c_int, C.c_float, vp, vp, vp, C.c_size_t, vp]),
+    "qst_community_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "qst_community_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, C.c_size_t, vp]),
+    "qst_community_members": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
+                                        C.c_size_t, vp]),
+    "qst_community_claim": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]),
+    "qst_community_rescore": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int64, vp, vp]),
     "qst_shadow_matrix": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
     "qst_shadow_all": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "qst_gemm_nt_x3": (C.c_int, [C.POINTER(QstGemmArgs), C.c_int, vp]),

@@ -12,6 +12,9 @@
 //
 // qst_topk_stream does the same chunk by chunk for a corpus of any size: each chunk's score block is merged into a
 // running [nq, k] result by topk_merge_kernel, whose ties are decided by global id, so the chunking does not show.
+//
+// qst_community_* (at the end of the file) are sentence-transformers 2.2.2's util.community_detection on the same panels:
+// a count per row, the members of the rows that are asked for, and the greedy claim -- no n x n matrix, no top-k.
 #include "qst_common.h"
 #include "qst_kernels.h"
 
@@ -498,6 +501,234 @@ extern "C" int qst_score_matrix(const float* queries, const float* corpus, int n
 extern "C" int qst_normalize_rows(const float* x, int n, int dim, float* out, void* stream) {
     if (!x || !out || n <= 0 || dim <= 0) return QST_ERR_BAD_ARG;
     prep_rows_kernel<<<(n + 3) / 4, 256, 0, (hipStream_t)stream>>>(x, n, n, dim, 1, out);
+    QST_LAUNCH_CHECK();
+    return QST_OK;
+}
+
+// ---------------------------------------------------------------- community detection (ST 2.2.2 util.community_detection)
+// What the clustering needs from the n x n cosine scores is a count per row and, for a few rows, the columns at or above
+// the threshold: neither needs the matrix or a top-k. Both passes walk the same [2048 row block] x [chunk] panels through
+// the same call (community_panel), so a score has the same bits in both and the member pass finds exactly what the count
+// pass counted. The rows are their own corpus: a chunk's operand is a slice of the prepared rows, not a second copy.
+namespace {
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// counts[row] += number of the row's first `cols` scores that are >= thr (a NaN is not). One workgroup per row, 16-byte
+// loads (the panel's rows are 16-byte aligned: ld % 4 == 0), one writer per row: launches on one stream need no atomics.
+// self_member (nullable): the row's own column, when this panel holds it, leaves whether it passed.
+__global__ __launch_bounds__(256) void count_ge_kernel(const float* sc, int64_t ld, int cols, float thr, int64_t row_base,
+                                                       int64_t col_base, int32_t* counts, uint8_t* self_member) {
+    __shared__ int part[4];
+    const int tid = threadIdx.x;
+    const float* row = sc + (size_t)blockIdx.x * ld;
+    const int c4 = cols >> 2;
+    int c = 0;
+    for (int i = tid; i < c4; i += 256) {
+        const f32x4 v = *(const f32x4*)(row + 4 * (size_t)i);
+        c += (v[0] >= thr) + (v[1] >= thr) + (v[2] >= thr) + (v[3] >= thr);
+    }
+    for (int i = 4 * c4 + tid; i < cols; i += 256) c += row[i] >= thr;
+    c = wave_sum_i32(c);
+    if ((tid & 63) == 0) part[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) {
+        counts[blockIdx.x] += part[0] + part[1] + part[2] + part[3];
+        const int64_t own = row_base + blockIdx.x - col_base;
+        if (self_member && own >= 0 && own < cols) self_member[blockIdx.x] = row[own] >= thr ? 1 : 0;
+    }
+}
+
+// The columns of one chunk that pass, appended to the row's slot in ascending column order: one workgroup per wanted row
+// (begin >= 0), 256 columns a trip. Each wave ballots its 64 columns; a lane's place is the row's cursor + the counts of
+// the waves before it (fixed wave order, through LDS) + the set bits below it. The cursor lives in written[row] between
+// chunks. No atomics; nothing is stored at or past begin + capacity, but the cursor counts everything that passed.
+__global__ __launch_bounds__(256) void compact_ge_kernel(const float* sc, int64_t ld, int cols, float thr, int32_t col_base,
+                                                         const int64_t* begin, const int32_t* capacity, int32_t* out_index,
+                                                         float* out_score, int32_t* written) {
+    __shared__ int wc[2][4];                                // two sets: one barrier a trip is enough
+    const int64_t b = begin[blockIdx.x];
+    if (b < 0) return;                                      // (uniform)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* row = sc + (size_t)blockIdx.x * ld;
+    const int cap = capacity[blockIdx.x];
+    int cursor = written[blockIdx.x];
+    int set = 0;
+    for (int t0 = 0; t0 < cols; t0 += 256, set ^= 1) {
+        const int col = t0 + tid;
+        const float v = col < cols ? row[col] : 0.f;
+        const bool ok = col < cols && v >= thr;
+        const unsigned long long m = __ballot(ok);
+        if (lane == 0) wc[set][wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int x = wc[set][w];
+            total += x;
+            before += w < wave ? x : 0;
+        }
+        if (ok) {
+            const int pos = cursor + before + __popcll(m & ((1ull << lane) - 1ull));
+            if (pos < cap) {
+                out_index[b + pos] = col_base + col;
+                out_score[b + pos] = v;
+            }
+        }
+        cursor += total;
+    }
+    if (tid == 0) written[blockIdx.x] = cursor;            // every thread read it before the first barrier
+}
+
+// Greedy claim, in the given order, by ONE workgroup: candidate c is accepted when none of its members is taken, and then
+// takes them all; the barrier between candidates makes its marks visible to the next one's reads.
+__global__ __launch_bounds__(256) void claim_kernel(const int64_t* begin, const int32_t* len, int ncand, const int32_t* members,
+                                                    int n, uint8_t* taken, uint8_t* accepted) {
+    const int tid = threadIdx.x;
+    for (int c = 0; c < ncand; ++c) {
+        const int64_t b = begin[c];
+        const int L = len[c];
+        int clash = (b < 0 || L <= 0) ? 1 : 0;
+        if (!clash)
+            for (int i = tid; i < L; i += 256) {
+                const int j = members[b + i];
+                clash |= (j < 0 || j >= n) ? 1 : (int)taken[j];
+            }
+        clash = __syncthreads_or(clash);
+        if (!clash)
+            for (int i = tid; i < L; i += 256) taken[members[b + i]] = 1;
+        if (tid == 0) accepted[c] = clash ? 0 : 1;
+        __syncthreads();
+    }
+}
+
+// out[p] = cosine of rows a[p] and b[p] in fp64 from the rows as given (norms clamped at 1e-12): one wave per pair.
+__global__ __launch_bounds__(256) void pair_cos_f64_kernel(const float* x, int n, int dim, const int32_t* a, const int32_t* b,
+                                                           int64_t count, double* out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= count) return;
+    const int ia = a[p], ib = b[p];
+    if (ia < 0 || ia >= n || ib < 0 || ib >= n) {
+        if (lane == 0) out[p] = __builtin_nan("");
+        return;
+    }
+    const float* xa = x + (size_t)ia * dim;
+    const float* xb = x + (size_t)ib * dim;
+    double ab = 0.0, aa = 0.0, bb = 0.0;
+    for (int c = lane; c < dim; c += 64) {
+        const double u = xa[c], v = xb[c];
+        ab += u * v; aa += u * u; bb += v * v;
+    }
+    ab = wave_sum_f64(ab); aa = wave_sum_f64(aa); bb = wave_sum_f64(bb);
+    if (lane == 0) out[p] = ab / (fmax(sqrt(aa), 1e-12) * fmax(sqrt(bb), 1e-12));
+}
+
+// prepared rows: n rounded up to 4, plus 4 -- the last chunk's operand is read to 4 rows past its start + cols rounded up
+inline size_t community_rows(int n) { return pad4((size_t)n) + 4; }
+
+// argument checks shared by the two passes; `chunk` comes back clamped to n
+int community_check(const float* emb, int n, int dim, float threshold, int& chunk, const void* ws, size_t ws_bytes) {
+    if (!emb || !ws || n <= 0 || dim <= 0 || chunk <= 0 || threshold != threshold) return QST_ERR_BAD_ARG;
+    if (dim % 32 != 0) return QST_ERR_UNSUPPORTED;
+    if (chunk > n) chunk = n;
+    if (ws_bytes < qst_community_workspace_bytes(n, chunk, dim)) return QST_ERR_WORKSPACE;
+    if ((int64_t)pad4(chunk) * dim * 4 >= 0x7FFFFF00LL) return QST_ERR_UNSUPPORTED;
+    return QST_OK;
+}
+
+// the one way either pass gets a panel: rows [r0, r0 + rows) against rows [c0, c0 + cols) of the prepared rows `en`
+int community_panel(const float* en, int dim, int r0, int rows, int c0, int cols, float* sc, hipStream_t st) {
+    return score_block(en + (size_t)r0 * dim, en + (size_t)c0 * dim, rows, cols, (int)pad4(cols), dim, QST_SCORE_COS, sc, st);
+}
+
+int community_prepare(const float* emb, int n, int dim, float* en, hipStream_t st) {
+    const int np = (int)community_rows(n);
+    prep_rows_kernel<<<(np + 3) / 4, 256, 0, st>>>(emb, n, np, dim, 1, en);
+    QST_LAUNCH_CHECK();
+    return QST_OK;
+}
+
+}  // namespace
+
+extern "C" size_t qst_community_workspace_bytes(int n, int chunk, int dim) {
+    if (n <= 0 || chunk <= 0 || dim <= 0) return 0;
+    if (chunk > n) chunk = n;
+    const size_t rows = (size_t)(n < kQueryBlock ? n : kQueryBlock);
+    return (community_rows(n) * dim + rows * pad4((size_t)chunk)) * sizeof(float) + 1024;
+}
+
+extern "C" int qst_community_count(const float* emb, int n, int dim, float threshold, int chunk, int32_t* counts,
+                                   uint8_t* self_member, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!counts) return QST_ERR_BAD_ARG;
+    int rc = community_check(emb, n, dim, threshold, chunk, workspace, workspace_bytes);
+    if (rc != QST_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    float* en = (float*)workspace;
+    float* sc = en + community_rows(n) * dim;
+    rc = community_prepare(emb, n, dim, en, st);
+    if (rc != QST_OK) return rc;
+    QST_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n * sizeof(int32_t), st));
+    if (self_member) QST_HIP_CHECK(hipMemsetAsync(self_member, 0, (size_t)n, st));
+    for (int r0 = 0; r0 < n; r0 += kQueryBlock) {
+        const int rows = n - r0 < kQueryBlock ? n - r0 : kQueryBlock;
+        for (int c0 = 0; c0 < n; c0 += chunk) {
+            const int cols = n - c0 < chunk ? n - c0 : chunk;
+            rc = community_panel(en, dim, r0, rows, c0, cols, sc, st);
+            if (rc != QST_OK) return rc;
+            count_ge_kernel<<<rows, 256, 0, st>>>(sc, (int64_t)pad4(cols), cols, threshold, r0, c0, counts + r0,
+                                                  self_member ? self_member + r0 : nullptr);
+            QST_LAUNCH_CHECK();
+        }
+    }
+    return QST_OK;
+}
+
+extern "C" int qst_community_members(const float* emb, int n, int dim, float threshold, int chunk, int row0,
+                                     const int64_t* begin, const int32_t* capacity, int32_t* out_index, float* out_score,
+                                     int32_t* written, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!begin || !capacity || !out_index || !out_score || !written) return QST_ERR_BAD_ARG;
+    int rc = community_check(emb, n, dim, threshold, chunk, workspace, workspace_bytes);
+    if (rc != QST_OK) return rc;
+    if (row0 < 0 || row0 >= n || row0 % kQueryBlock != 0) return QST_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    float* en = (float*)workspace;
+    float* sc = en + community_rows(n) * dim;
+    rc = community_prepare(emb, n, dim, en, st);
+    if (rc != QST_OK) return rc;
+    const int rows = n - row0 < kQueryBlock ? n - row0 : kQueryBlock;
+    QST_HIP_CHECK(hipMemsetAsync(written, 0, (size_t)rows * sizeof(int32_t), st));
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int cols = n - c0 < chunk ? n - c0 : chunk;
+        rc = community_panel(en, dim, row0, rows, c0, cols, sc, st);
+        if (rc != QST_OK) return rc;
+        compact_ge_kernel<<<rows, 256, 0, st>>>(sc, (int64_t)pad4(cols), cols, threshold, c0, begin, capacity, out_index,
+                                                out_score, written);
+        QST_LAUNCH_CHECK();
+    }
+    return QST_OK;
+}
+
+extern "C" int qst_community_claim(const int64_t* begin, const int32_t* len, int ncand, const int32_t* members, int n,
+                                   uint8_t* taken, uint8_t* accepted, void* stream) {
+    if (ncand < 0 || n <= 0 || !taken) return QST_ERR_BAD_ARG;
+    if (ncand == 0) return QST_OK;
+    if (!begin || !len || !members || !accepted) return QST_ERR_BAD_ARG;
+    claim_kernel<<<1, 256, 0, (hipStream_t)stream>>>(begin, len, ncand, members, n, taken, accepted);
+    QST_LAUNCH_CHECK();
+    return QST_OK;
+}
+
+extern "C" int qst_community_rescore(const float* emb, int n, int dim, const int32_t* rows_a, const int32_t* rows_b,
+                                     int64_t count, double* out, void* stream) {
+    if (!emb || n <= 0 || dim <= 0 || count < 0) return QST_ERR_BAD_ARG;
+    if (count == 0) return QST_OK;
+    if (!rows_a || !rows_b || !out) return QST_ERR_BAD_ARG;
+    if ((count + 3) / 4 > 0x7FFFFFFFLL) return QST_ERR_UNSUPPORTED;
+    pair_cos_f64_kernel<<<(unsigned)((count + 3) / 4), 256, 0, (hipStream_t)stream>>>(emb, n, dim, rows_a, rows_b, count, out);
     QST_LAUNCH_CHECK();
     return QST_OK;
 }

@@ -3,7 +3,9 @@ cos_sim, dot_score, batch_to_device -- plus euclidean_score, the reference's own
 (models/evaluators.py:392-405). All three score matrices come from libqst (qst_score_matrix: row normalisation, the
 split-bf16 x3 GEMM or the direct-difference Euclidean kernel); there is no torch arithmetic and no CPU path here.
 semantic_search, paraphrase_mining and paraphrase_mining_embeddings (ST 2.2.2 signatures) stand on the streaming top-k
-(qst_topk_stream / qst_topk_merge_rows); of them only merge_mined_pairs, the pair bookkeeping, is host numpy."""
+(qst_topk_stream / qst_topk_merge_rows); of them only merge_mined_pairs, the pair bookkeeping, is host numpy.
+community_detection (ST 2.2.2) counts, extracts and claims on the device (qst_community_*), with no n x n matrix; its
+candidate order, round planning and the final order inside a community are host numpy."""
 from __future__ import annotations
 
 import numpy as np
@@ -325,6 +327,173 @@ def paraphrase_mining(model, sentences, show_progress_bar: bool = False, batch_s
     paraphrase_mining_embeddings. Returns [score, i, j] with i < j indexing `sentences`."""
     emb = model.encode(list(sentences), show_progress_bar=show_progress_bar, batch_size=batch_size, convert_to_tensor=True)
     return paraphrase_mining_embeddings(emb, query_chunk_size, corpus_chunk_size, max_pairs, top_k, score_function)
+
+
+# Members (row number + score, 8 bytes each) that one round of community_detection extracts at most, beyond its first
+# candidate: 2^26 members = 512 MB. A bound on memory in round numbers, not a tuned value; the result does not depend on it.
+COMMUNITY_ROUND_MEMBERS = 1 << 26
+_ROW_BLOCK = 2048                    # rows per score panel (csrc/retrieval.hip: kQueryBlock)
+
+
+def community_order(counts, min_community_size: int):
+    """The candidate rows (counts >= min_community_size) in greedy order: larger community first, lower row first among
+    equal sizes. Pure numpy."""
+    counts = np.asarray(counts, dtype=np.int64)
+    idx = np.flatnonzero(counts >= min_community_size)
+    return idx[np.lexsort((idx, -counts[idx]))]
+
+
+def plan_community_round(order, counts, self_member, taken, start: int, budget: int):
+    """The next round of community_detection, pure numpy: walking order[start:], the candidates whose members are to be
+    extracted, until their counts sum past `budget` (the first one is always taken, so a round makes progress). A
+    candidate whose own row is taken is dropped here -- it could only be rejected -- but only where the row is a member of
+    its own community (self_member): a zero or NaN row is not, and its community is still to be looked at.
+    Returns (rows of the round in greedy order, the position in `order` where the next round starts)."""
+    order = np.asarray(order, dtype=np.int64)
+    cand = order[start:]
+    if len(cand) == 0:
+        return cand, len(order)
+    live = ~(np.asarray(taken, dtype=bool)[cand] & np.asarray(self_member, dtype=bool)[cand])
+    if not live.any():
+        return cand[:0], len(order)
+    cost = np.cumsum(np.where(live, np.asarray(counts, dtype=np.int64)[cand], 0))
+    stop = int(np.searchsorted(cost, budget, side="right"))          # leading candidates whose running sum fits
+    stop = max(stop, int(np.argmax(live)) + 1)
+    return cand[:stop][live[:stop]], start + stop
+
+
+def order_community(centre: int, members, scores):
+    """One community in the order of ST's "the first element is the central point": the candidate row first when it is a
+    member, the rest by (score descending, row ascending). Pure numpy; returns a list of int."""
+    members = np.asarray(members, dtype=np.int64)
+    order = np.lexsort((members, -np.asarray(scores, dtype=np.float64)))
+    out = [int(m) for m in members[order]]
+    if centre in out:
+        out.remove(centre)
+        out.insert(0, int(centre))
+    return out
+
+
+def _community_detection(e: torch.Tensor, threshold: float, min_community_size: int, chunk: int, stats=None):
+    """community_detection on prepared device rows e [n, dim % 32 == 0]. stats (a dict, for tools/community_bench.py):
+    filled with the seconds of the count pass and, per round, candidates / members / row blocks / seconds."""
+    import time
+    from . import _lib
+    lib = _lib.load()
+    n, dim = e.shape
+    dev = e.device
+    sp = _lib.current_stream_ptr
+
+    def clock():
+        if stats is not None:
+            torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.qst_community_workspace_bytes(n, chunk, dim), dtype=torch.uint8, device=dev)
+        counts_d = torch.empty(n, dtype=torch.int32, device=dev)
+        self_d = torch.empty(n, dtype=torch.uint8, device=dev)
+        t0 = clock()
+        _lib.check(lib.qst_community_count(e.data_ptr(), n, dim, threshold, chunk, counts_d.data_ptr(), self_d.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), sp()), "qst_community_count")
+        counts = counts_d.cpu().numpy()
+        self_member = self_d.cpu().numpy().astype(bool)
+        if stats is not None:
+            stats.update(count_s=clock() - t0, rounds=[])
+        order = community_order(counts, min_community_size)
+        taken = np.zeros(n, dtype=bool)
+        taken_d = torch.zeros(n, dtype=torch.uint8, device=dev)
+        written_d = torch.empty(n, dtype=torch.int32, device=dev)
+        communities, start = [], 0
+        while start < len(order):
+            picked, start = plan_community_round(order, counts, self_member, taken, start, COMMUNITY_ROUND_MEMBERS)
+            if len(picked) == 0:
+                break
+            t0 = clock()
+            lens = counts[picked].astype(np.int64)
+            begins = np.cumsum(lens) - lens
+            total = int(lens.sum())
+            row_begin = np.full(n, -1, dtype=np.int64)
+            row_begin[picked] = begins
+            begin_d = torch.from_numpy(row_begin).to(dev)
+            index_d = torch.empty(total, dtype=torch.int32, device=dev)
+            score_d = torch.empty(total, dtype=torch.float32, device=dev)
+            blocks = np.unique(picked // _ROW_BLOCK)
+            for blk in blocks:
+                r0 = int(blk) * _ROW_BLOCK
+                _lib.check(lib.qst_community_members(e.data_ptr(), n, dim, threshold, chunk, r0, begin_d.data_ptr() + 8 * r0,
+                                                     counts_d.data_ptr() + 4 * r0, index_d.data_ptr(), score_d.data_ptr(),
+                                                     written_d.data_ptr() + 4 * r0, ws.data_ptr(), ws.numel(), sp()),
+                           "qst_community_members")
+            picked_d = torch.from_numpy(picked).to(dev)
+            if not torch.equal(written_d[picked_d], counts_d[picked_d]):
+                raise _lib.QstError("community_detection: the member pass and the count pass disagree")
+            t1 = clock()
+            cand_begin = torch.from_numpy(begins).to(dev)
+            cand_len = torch.from_numpy(lens.astype(np.int32)).to(dev)
+            accepted_d = torch.empty(len(picked), dtype=torch.uint8, device=dev)
+            _lib.check(lib.qst_community_claim(cand_begin.data_ptr(), cand_len.data_ptr(), len(picked), index_d.data_ptr(), n,
+                                               taken_d.data_ptr(), accepted_d.data_ptr(), sp()), "qst_community_claim")
+            won = np.flatnonzero(accepted_d.cpu().numpy())
+            if len(won):
+                # only the accepted communities come back, with fp64 cosines for the order inside them: equally similar
+                # rows must tie exactly, which the x3 scores do not promise in their last bits
+                members_d = torch.cat([index_d[int(begins[c]):int(begins[c] + lens[c])] for c in won])
+                centres_d = torch.from_numpy(np.repeat(picked[won], lens[won]).astype(np.int32)).to(dev)
+                exact_d = torch.empty(members_d.numel(), dtype=torch.float64, device=dev)
+                _lib.check(lib.qst_community_rescore(e.data_ptr(), n, dim, centres_d.data_ptr(), members_d.data_ptr(),
+                                                     members_d.numel(), exact_d.data_ptr(), sp()), "qst_community_rescore")
+                members, exact = members_d.cpu().numpy(), exact_d.cpu().numpy()
+                ends = np.cumsum(lens[won])
+                for c, b, t in zip(won, ends - lens[won], ends):
+                    communities.append(order_community(int(picked[c]), members[b:t], exact[b:t]))
+            taken = taken_d.cpu().numpy().astype(bool)
+            if stats is not None:
+                t2 = clock()
+                stats["rounds"].append(dict(candidates=int(len(picked)), members=total, row_blocks=int(len(blocks)),
+                                            accepted=int(len(won)), members_s=t1 - t0, claim_s=t2 - t1))
+    return communities
+
+
+def community_detection(embeddings, threshold: float = 0.75, min_community_size: int = 10, init_max_size: int = 1000, *,
+                        corpus_chunk_size: int = STREAM_CHUNK):
+    """sentence_transformers.util.community_detection (2.2.2), "fast clustering": the communities of rows whose cosine
+    similarity to a central row is at least `threshold`, as a list of lists of int, largest first, no row in two of them.
+
+    With S the cosine scores (rows normalised with eps 1e-12, as cos_sim) and N(i) = {j : S[i, j] >= threshold} -- the row
+    itself when its own score passes, a NaN score passes nothing -- row i is a candidate when |N(i)| >= min_community_size.
+    Candidates are taken by (|N(i)| descending, i ascending); one is accepted when none of its members belongs to a
+    community accepted before it, and is then returned whole (a rejected one is dropped whole, not trimmed). Inside a
+    community the candidate row comes first, the rest by (score descending, row ascending).
+
+    Device: no [n, n] matrix and no top-k. One pass over the [2048, chunk] score panels counts |N(i)|
+    (qst_community_count); then, in rounds that bound memory (COMMUNITY_ROUND_MEMBERS), the members of the next
+    candidates in greedy order are compacted out of the same panels (qst_community_members), claimed on the device
+    (qst_community_claim) and only the accepted communities are copied back, ordered by fp64 cosines
+    (qst_community_rescore). Inputs: a tensor, a numpy array or a list of tensors; they are moved to the HIP device
+    (there is no CPU path).
+
+    Deliberate differences from ST 2.2.2: init_max_size is checked (a positive int) but changes nothing -- ST uses it only
+    as the width of its top-k shortcut and, in a community larger than it, falls back to index order; here the order is
+    always the one above. min_community_size > n returns [] where ST's topk raises. min_community_size < 1 or a NaN
+    threshold raises ValueError. corpus_chunk_size (keyword-only) bounds memory only."""
+    if isinstance(min_community_size, bool) or int(min_community_size) != min_community_size or min_community_size < 1:
+        raise ValueError(f"min_community_size must be a positive int (got {min_community_size!r})")
+    if isinstance(init_max_size, bool) or not isinstance(init_max_size, (int, np.integer)) or init_max_size < 1:
+        raise ValueError(f"init_max_size must be a positive int (got {init_max_size!r})")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold must not be NaN")
+    if isinstance(corpus_chunk_size, bool) or int(corpus_chunk_size) != corpus_chunk_size or corpus_chunk_size < 1:
+        raise ValueError(f"corpus_chunk_size must be a positive int (got {corpus_chunk_size!r})")
+    rows = _as_rows(embeddings)
+    n = rows.shape[0]
+    if rows.dim() != 2:
+        raise ValueError(f"embeddings must be rows of one width (got shape {tuple(rows.shape)})")
+    if n == 0 or int(min_community_size) > n:
+        return []
+    e = _device_rows(rows)
+    return _community_detection(e, threshold, int(min_community_size), min(int(corpus_chunk_size), n))
 
 
 def mine_hard_negatives(references, candidates, k: int, threshold: float = 0.2, embedder=None, batch_size: int = 64):
