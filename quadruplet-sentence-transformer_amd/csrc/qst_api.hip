@@ -15,7 +15,7 @@
 static thread_local int g_last_hip_error = 0;
 extern "C" int qst_set_hip_error(int code) { g_last_hip_error = code; return code; }
 extern "C" int qst_last_hip_error(void) { return g_last_hip_error; }
-extern "C" int qst_version(void) { return 111; }
+extern "C" int qst_version(void) { return 112; }
 
 extern "C" const char* qst_strerror(int s) {
     switch (s) {
@@ -405,10 +405,14 @@ MxOperands plan_mx_train_operands(const qst_config& c, int nseq, int L, size_t b
     MxOperands t;
     const size_t M = (size_t)nseq * L, H = c.hidden_size, I = c.intermediate_size;
     Bump take{base};
-    t.xq = take(M * H); t.xs = take(M * H / 32 + 1024);
-    t.cq = take(M * H); t.cs = take(M * H / 32 + 1024);
-    t.yq = take(M * H); t.ys = take(M * H / 32 + 1024);
-    t.hq = take(M * I); t.hs = take(M * I / 32 + 1024);
+    // scales: stage-major [K / 128][M][4] bytes = M * K / 32 exactly (K % 128 == 0), as plan_mx sizes them. Every writer
+    // (ln_row_finish, the GELU_MX_TRAIN and GEMM + LayerNorm epilogues, qst_quant_mx) and every reader (the fp8 GEMMs' scale
+    // loads) stops at row M - 1: the same kernels run on plan_mx's unpadded arrays. (Until version 112 each array carried
+    // 1024 further bytes that nothing wrote or read; tests/test_gpu_encoder_arenas.py holds the last one against its band.)
+    t.xq = take(M * H); t.xs = take(M * H / 32);
+    t.cq = take(M * H); t.cs = take(M * H / 32);
+    t.yq = take(M * H); t.ys = take(M * H / 32);
+    t.hq = take(M * I); t.hs = take(M * I / 32);
     t.total = take.off;
     return t;
 }
