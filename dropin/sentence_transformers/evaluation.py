@@ -4,7 +4,7 @@ from quadruplet_sentence_transformer_amd.evaluation import (BinaryClassification
                                                             MSEEvaluator,
                                                             ParaphraseMiningEvaluator,
                                                             QuadrupletEvaluator,
-                                                            QuadrupletLossEvaluator, SentenceEvaluator,
+                                                            QuadrupletLossEvaluator, RerankingEvaluator, SentenceEvaluator,
                                                             SequentialEvaluator, SimilarityFunction, TranslationEvaluator,
                                                             TripletEvaluator,
                                                             get_sequential_evaluator)

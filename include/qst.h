@@ -521,6 +521,47 @@ size_t qst_binary_eval_workspace_bytes(int64_t n, int nsets);
 int qst_binary_eval(const float* scores, const int64_t* labels, int64_t n, int nsets, const int32_t* high_is_similar,
                     double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * What sentence-transformers 2.2.2's evaluation.RerankingEvaluator computes for nq queries, each with its own candidate
+ * documents (version 113; csrc/rerank.hip). The groups are ragged and shared by both entry points: query g owns the
+ * documents offsets[g] .. offsets[g + 1] - 1 of the flat arrays (offsets[0] == 0, offsets[nq] == nd), the first num_pos[g]
+ * of them its positives and the rest its negatives (upstream's [True] * num_pos + [False] * num_neg).
+ *   offsets : int64 [nq + 1] (device), num_pos : int32 [nq] (device)
+ * qst_rerank_scores: scores[j] f32 [nd] = the score of document j against the query of its group. queries f32 [nq, dim],
+ * docs f32 [nd, dim] (device, contiguous), any dim >= 1 (rows are read 16 bytes a lane where dim % 4 == 0 and both arrays
+ * are 16-byte aligned, element by element otherwise). mode: QST_SCORE_COS (util.cos_sim: each side divided by
+ * max(|x|, 1e-12); a zero row scores 0), QST_SCORE_DOT or QST_SCORE_EUCLID (1 / (1 + |q - d|_2)); products and sums in
+ * fp32. Four consecutive documents to a wave; a group is found by a binary search that reads offsets[1 .. nq - 1] only.
+ * qst_rerank_metrics works from scores alone (any similarity may have made them; the larger the better, floats compared
+ * as floats, -0.0 == +0.0). For every positive p of a group, over the documents d of that group:
+ *   rank(p)   = 1 + |{ d : s_d > s_p, or s_d == s_p and d < p }|    its place in a stable descending sort
+ *                                                                    (numpy.argsort(-s, kind="stable")): among equal
+ *                                                                    scores the earlier document comes first
+ *   ge_all(p) = |{ d : s_d >= s_p }|,  ge_pos(p) = |{ positives d : s_d >= s_p }|
+ *   per_query : f64 [nq, 3] (device) = {rr, ap, ndcg} with P = num_pos[g]:
+ *     rr   = 1 / min_p rank(p) where that minimum is <= k, else 0                       (upstream's MRR@k term)
+ *     ap   = (1 / P) sum_p ge_pos(p) / ge_all(p)                                        (sklearn's average_precision_score)
+ *     ndcg = sum_{p : rank(p) <= k} 1 / log2(1 + rank(p)) / sum_{i = 1 .. min(P, k)} 1 / log2(1 + i)
+ *   out       : f64 [5] (device) = {mean rr, mean ap, mean ndcg, non-finite scores inside valid groups, invalid groups};
+ *               the means run over the valid groups (none: 0)
+ * A group is valid when 0 <= lo < hi <= nd and 1 <= num_pos < hi - lo. An invalid one is counted in out[4], its per_query
+ * row is 0, it contributes nothing, and none of its scores is read: the check comes before any read of scores, so offsets
+ * and num_pos of any content cause no access outside the arrays (offsets that are not ascending give valid-looking groups
+ * unspecified numbers). A NaN or infinite score has no rank: it is counted in out[3] and the numbers of its group mean
+ * nothing. Nothing is sorted and a group may have any size: a counting pass, the wave of a positive document striding its group, writes
+ * {rank, ge_pos, ge_all}; a pass of one workgroup per query adds the terms in double, in document order; one workgroup
+ * takes the means in a fixed order. No atomics, integer counts, the same inputs give the same bits, on the caller's
+ * stream without host synchronisation.
+ * A NULL pointer, nq < 1, nd < 2, k < 1, dim < 1, another mode, a workspace that is not 16-byte aligned or shorter than
+ * qst_rerank_workspace_bytes (16 bytes per document and 4 per query, rounded up to 16; 0 for sizes outside the limits):
+ * QST_ERR_BAD_ARG. nd >= 2^31 or nq >= 2^31: QST_ERR_UNSUPPORTED. Both before any launch, nothing written.
+ */
+int qst_rerank_scores(const float* queries, const float* docs, const int64_t* offsets, int64_t nq, int64_t nd, int dim,
+                      int mode, float* scores, void* stream);
+size_t qst_rerank_workspace_bytes(int64_t nq, int64_t nd);
+int qst_rerank_metrics(const float* scores, const int64_t* offsets, const int32_t* num_pos, int64_t nq, int64_t nd, int k,
+                       double* per_query, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Retrieval scoring for the encode()-driven evaluators: what sentence-transformers'
  * InformationRetrievalEvaluator does per corpus chunk -- util.cos_sim / util.dot_score of the query embeddings
  * against the chunk, then torch.topk(k) (reference call sites models/evaluators.py:572-588,

@@ -120,6 +120,9 @@ SIGNATURES = {
     "qst_softmax_ce": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp]),
     "qst_binary_eval_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "qst_binary_eval": (C.c_int, [vp, vp, C.c_int64, C.c_int, c_i32p, vp, vp, C.c_size_t, vp]),
+    "qst_rerank_scores": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int, vp, vp]),
+    "qst_rerank_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "qst_rerank_metrics": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "qst_shadow8_bytes": (C.c_int64, [C.POINTER(QstConfig)]),
     "qst_clip_adamw_step_sched": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                             C.c_float, C.c_float, C.c_int64, C.c_int64, vp, vp, vp, vp]),

@@ -6,7 +6,8 @@ ParaphraseMiningEvaluator (util.paraphrase_mining on the streaming top-k, qst_to
 distillation, MSEEvaluator (qst_embed_mse) and TranslationEvaluator (two k = 1 searches of the streaming top-k), and
 LabelAccuracyEvaluator, which scores the classifier of losses.SoftmaxLoss (qst_softmax_ce's counts), and
 BinaryClassificationEvaluator for the contrastive pair losses (best accuracy and F1 cuts and the average precision of
-four pair scores, counted without a sort by qst_binary_eval). The two
+four pair scores, counted without a sort by qst_binary_eval), and RerankingEvaluator for the ranking losses (MAP, MRR@k
+and NDCG@k of every query's own candidate list: qst_rerank_scores and qst_rerank_metrics over ragged groups). The two
 evaluators the reference selects its models with, QuadrupletEvaluator (qst_quadruplet_eval) and QuadrupletLossEvaluator, and the chain
 get_sequential_evaluator builds of them stand at the end."""
 from __future__ import annotations
@@ -771,6 +772,123 @@ class BinaryClassificationEvaluator(SentenceEvaluator):
         """(the best F1, its precision, its recall, its threshold) of upstream's walk over the sorted pairs."""
         r = BinaryClassificationEvaluator._best_cuts(scores, labels, high_score_more_similar)
         return r["f1"], r["precision"], r["recall"], r["f1_threshold"]
+
+
+def cos_sim(a, b):
+    """util.cos_sim, bound on the first call (util brings torch in; this module does not): RerankingEvaluator's default
+    similarity_fct, with util.cos_sim's mode tag."""
+    from . import util
+    return util.cos_sim(a, b)
+
+
+cos_sim._qst_mode = 1
+
+
+class RerankingEvaluator(SentenceEvaluator):
+    """sentence-transformers 2.2.2's RerankingEvaluator, the one the re-ranking and unsupervised recipes select their
+    checkpoints with: samples {'query': str, 'positive': [str, ...], 'negative': [str, ...]}; every query's candidates are
+    ranked by similarity_fct and the mean average precision (the return value) and MRR@mrr_at_k are reported;
+    compute_metrices adds NDCG@mrr_at_k, which upstream gained later. Every distinct text, queries and documents together,
+    goes through ONE encode call; the candidates of all queries form one flat array with ragged groups, scored by one
+    qst_rerank_scores launch (cosine, dot product or the Euclidean score; any other callable is called once per query, as
+    upstream calls it, and its results are concatenated on the device) and turned into the metrics by one
+    qst_rerank_metrics call (csrc/rerank.hip: counts per positive, no sort); five numbers come back to the host. Upstream
+    runs a cos_sim, an argsort, a Python walk and an sklearn call per query.
+
+    Equal scores: the document that comes first in positive + negative ranks first (a stable descending sort). Upstream's
+    torch.argsort(-scores) is not stable, so it gives no rule to reproduce; the average precision does not depend on it.
+    Samples without a positive or without a negative are dropped, as upstream drops them. use_batched_encoding is accepted
+    for the signature and changes nothing: the texts are always encoded in one batched call."""
+
+    def __init__(self, samples, mrr_at_k: int = 10, name: str = "", write_csv: bool = True, similarity_fct=cos_sim,
+                 batch_size: int = 64, show_progress_bar: bool = False, use_batched_encoding: bool = True):
+        self.samples = samples
+        self.name, self.mrr_at_k, self.similarity_fct = name, mrr_at_k, similarity_fct
+        self.batch_size, self.show_progress_bar, self.use_batched_encoding = batch_size, show_progress_bar, use_batched_encoding
+        if isinstance(self.samples, dict):
+            self.samples = list(self.samples.values())
+        self.samples = [s for s in self.samples if len(s["positive"]) > 0 and len(s["negative"]) > 0]
+        self.csv_file = "RerankingEvaluator" + ("_" + name if name else "") + "_results.csv"
+        self.csv_headers = ["epoch", "steps", "MAP", "MRR@{}".format(mrr_at_k)]
+        self.write_csv = write_csv
+
+    def _groups(self):
+        """(offsets [nq + 1], num_pos [nq]) of the flat document array: a query's positives, then its negatives."""
+        sizes = [len(s["positive"]) + len(s["negative"]) for s in self.samples]
+        offsets = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+        return offsets, np.asarray([len(s["positive"]) for s in self.samples], dtype=np.int32)
+
+    def _device_scores(self, model):
+        """(scores fp32 [nd] on the device, offsets, num_pos). The distinct texts, in first-seen order, go through one encode
+        call; the flat query and document arrays are index_selects of its result."""
+        import torch
+        from . import util
+        if not self.samples:
+            raise ValueError("RerankingEvaluator: no sample has both a positive and a negative document")
+        queries = [s["query"] for s in self.samples]
+        docs = [t for s in self.samples for t in list(s["positive"]) + list(s["negative"])]
+        texts = list(dict.fromkeys(queries + docs))
+        emb = model.encode(texts, batch_size=self.batch_size, show_progress_bar=self.show_progress_bar, convert_to_tensor=True)
+        index = {t: i for i, t in enumerate(texts)}
+        offsets, num_pos = self._groups()
+        with torch.no_grad():
+            q = emb.index_select(0, torch.tensor([index[t] for t in queries], dtype=torch.int64, device=emb.device))
+            d = emb.index_select(0, torch.tensor([index[t] for t in docs], dtype=torch.int64, device=emb.device))
+            how, fn = resolve_score_function(getattr(self.similarity_fct, "__name__", "similarity_fct"), self.similarity_fct,
+                                             emb.device)
+            if how == "native":
+                scores = util.rerank_scores(q, d, offsets, fn)
+            else:
+                rows = []
+                for g in range(len(queries)):
+                    r = torch.as_tensor(fn(q[g], d[offsets[g]:offsets[g + 1]]))
+                    rows.append((r[0] if r.dim() == 2 else r).reshape(-1).to(emb.device, torch.float32))
+                scores = torch.cat(rows)
+                if scores.numel() != len(docs):
+                    raise ValueError(f"RerankingEvaluator: similarity_fct returned {scores.numel()} scores for {len(docs)} documents")
+        return scores, offsets, num_pos
+
+    def _metrics(self, model, want_table: bool = False):
+        import torch
+        from . import _lib, util
+        scores, offsets, num_pos = self._device_scores(model)
+        with torch.no_grad():
+            per_query, out = util.rerank_metrics(scores, offsets, num_pos, self.mrr_at_k)
+            host = out.cpu().numpy()                                # the one copy to the host
+        if host[3] > 0:
+            raise ValueError(f"RerankingEvaluator: {int(host[3])} scores are NaN or infinite; such scores have no rank")
+        if host[4] > 0:
+            raise _lib.QstError(f"RerankingEvaluator: qst_rerank_metrics could not use {int(host[4])} of {len(self.samples)} groups")
+        return host, (per_query.cpu().numpy() if want_table else None)
+
+    def compute_metrices(self, model) -> Dict[str, float]:
+        """{'map', 'mrr', 'ndcg'}: the means over the queries; mrr and ndcg within mrr_at_k."""
+        host, _ = self._metrics(model)
+        return {"map": float(host[1]), "mrr": float(host[0]), "ndcg": float(host[2])}
+
+    def per_query_metrics(self, model) -> np.ndarray:
+        """float64 [nq, 3]: {reciprocal rank within mrr_at_k, average precision, NDCG within mrr_at_k} of every query, in
+        the order of the samples."""
+        return self._metrics(model, want_table=True)[1]
+
+    def __call__(self, model, output_path: str = None, epoch: int = -1, steps: int = -1) -> float:
+        if epoch != -1:
+            out_txt = " after epoch {}:".format(epoch) if steps == -1 else " in epoch {} after {} steps:".format(epoch, steps)
+        else:
+            out_txt = ":"
+        LOGGER.info("RerankingEvaluator: Evaluating the model on " + self.name + " dataset" + out_txt)
+        scores = self.compute_metrices(model)
+        mean_ap, mean_mrr = scores["map"], scores["mrr"]
+        num_positives = [len(s["positive"]) for s in self.samples]
+        num_negatives = [len(s["negative"]) for s in self.samples]
+        LOGGER.info("Queries: {} \t Positives: Min {:.1f}, Mean {:.1f}, Max {:.1f} \t Negatives: Min {:.1f}, Mean {:.1f}, "
+                    "Max {:.1f}".format(len(self.samples), np.min(num_positives), np.mean(num_positives), np.max(num_positives),
+                                        np.min(num_negatives), np.mean(num_negatives), np.max(num_negatives)))
+        LOGGER.info("MAP: {:.2f}".format(mean_ap * 100))
+        LOGGER.info("MRR@{}: {:.2f}".format(self.mrr_at_k, mean_mrr * 100))
+        if output_path is not None and self.write_csv:
+            _append_csv(os.path.join(output_path, self.csv_file), self.csv_headers, [epoch, steps, mean_ap, mean_mrr])
+        return mean_ap
 
 
 def _unwrap_example(example):

@@ -5,7 +5,8 @@ split-bf16 x3 GEMM or the direct-difference Euclidean kernel); there is no torch
 semantic_search, paraphrase_mining and paraphrase_mining_embeddings (ST 2.2.2 signatures) stand on the streaming top-k
 (qst_topk_stream / qst_topk_merge_rows); of them only merge_mined_pairs, the pair bookkeeping, is host numpy.
 community_detection (ST 2.2.2) counts, extracts and claims on the device (qst_community_*), with no n x n matrix; its
-candidate order, round planning and the final order inside a community are host numpy."""
+candidate order, round planning and the final order inside a community are host numpy. rerank_scores and rerank_metrics
+(qst_rerank_*) score and rank every query's own candidate list, ragged groups of one flat array, for RerankingEvaluator."""
 from __future__ import annotations
 
 import numpy as np
@@ -148,6 +149,115 @@ def topk_rows(scores: torch.Tensor, k: int, index_map: torch.Tensor = None):
     _lib.check(lib.qst_topk_rows(s.data_ptr(), n, _lib.ptr(im), n_rows, n, k, out_s.data_ptr(), out_i.data_ptr(),
                                  _lib.current_stream_ptr()), "qst_topk_rows")
     return out_s, out_i
+
+
+# ------------------------------------------------------------------ re-ranking: ragged groups of one flat document array
+RERANK_MAX = (1 << 31) - 1           # queries, and documents, of one qst_rerank_* call
+
+
+def _on_host(x) -> bool:
+    return not (isinstance(x, torch.Tensor) and x.is_cuda)
+
+
+def _rerank_groups(what: str, offsets, num_pos, nd: int):
+    """(offsets int64 [nq + 1], num_pos int32 [nq] or None, nq), not yet moved. Host lists, arrays and tensors are checked
+    here, before anything touches the device -- ValueError names the first bad group; device tensors go through as they
+    are (the kernel counts the groups it cannot use)."""
+    from . import _lib
+    if _on_host(offsets):
+        o = np.asarray(offsets.numpy() if isinstance(offsets, torch.Tensor) else offsets)
+        if o.ndim != 1 or len(o) < 2 or not np.issubdtype(o.dtype, np.integer):
+            raise ValueError(f"{what}: offsets must be nq + 1 integers, nq >= 1 (got {o.dtype} of shape {o.shape})")
+        o = o.astype(np.int64)
+        if o[0] != 0:
+            raise ValueError(f"{what}: group 0 starts at offsets[0] = {o[0]}, not 0")
+        down = np.flatnonzero(np.diff(o) < 0)
+        if len(down):
+            g = int(down[0])
+            raise ValueError(f"{what}: group {g}: offsets descend, {o[g]} -> {o[g + 1]}")
+        if o[-1] != nd:
+            raise ValueError(f"{what}: group {len(o) - 2} ends at offsets[nq] = {o[-1]}, but there are {nd} documents")
+        sizes = np.diff(o)
+        offsets = torch.from_numpy(o)
+    else:
+        sizes = None
+    nq = int(offsets.numel()) - 1
+    if num_pos is not None:
+        if _on_host(num_pos):
+            p = np.asarray(num_pos.numpy() if isinstance(num_pos, torch.Tensor) else num_pos)
+            if p.ndim != 1 or len(p) != nq or not np.issubdtype(p.dtype, np.integer):
+                raise ValueError(f"{what}: num_pos must be {nq} integers, one per group (got {p.dtype} of shape {p.shape})")
+            p = p.astype(np.int64)
+            bad = np.flatnonzero(p < 1) if sizes is None else np.flatnonzero((p < 1) | (p >= sizes))
+            if len(bad):
+                g = int(bad[0])
+                size = "" if sizes is None else f" of {sizes[g]} documents"
+                raise ValueError(f"{what}: group {g}: {p[g]} positives{size}; a group needs 1 <= num_pos < its size")
+            num_pos = torch.from_numpy(p.astype(np.int32))
+        elif num_pos.numel() != nq:
+            raise ValueError(f"{what}: {num_pos.numel()} entries of num_pos for {nq} groups")
+    if nq < 1 or nd < 2:
+        raise ValueError(f"{what}: {nq} groups over {nd} documents; at least one group and two documents are needed")
+    if nq > RERANK_MAX or nd > RERANK_MAX:
+        raise _lib.QstError(f"{what}: {nq} groups over {nd} documents; the kernel takes up to {RERANK_MAX} (2^31 - 1) of each")
+    return offsets, num_pos, nq
+
+
+def rerank_scores(queries: torch.Tensor, docs: torch.Tensor, offsets, mode="cos") -> torch.Tensor:
+    """The score of every candidate document against the query of its group (libqst qst_rerank_scores): queries [nq, D],
+    docs [nd, D] HIP tensors, query g owning docs[offsets[g] : offsets[g + 1]]; mode 'cos' | 'dot' | 'euclid'. Returns fp32
+    [nd] on the device. offsets: nq + 1 ascending integers from 0 to nd -- a host list or array is checked first, a device
+    tensor is passed through. Current stream, nothing copied to the host, no CPU fallback."""
+    from . import _lib
+    queries, docs = torch.as_tensor(queries), torch.as_tensor(docs)
+    if queries.dim() != 2 or docs.dim() != 2 or queries.shape[1] != docs.shape[1] or queries.shape[1] < 1:
+        raise ValueError(f"rerank_scores: queries {tuple(queries.shape)} and docs {tuple(docs.shape)} must be [nq, D] and [nd, D]")
+    nd, dim = docs.shape
+    off, _, nq = _rerank_groups("rerank_scores", offsets, None, nd)
+    if queries.shape[0] != nq:
+        raise ValueError(f"rerank_scores: {queries.shape[0]} queries but offsets describe {nq} groups")
+    if not (queries.is_cuda and docs.is_cuda):
+        raise _lib.QstError("rerank_scores runs on the HIP device: pass CUDA tensors (there is no CPU fallback)")
+    lib = _lib.load()
+    q = queries.to(torch.float32).contiguous()
+    d = docs.to(q.device, torch.float32).contiguous()
+    off = off.to(q.device, torch.int64).contiguous()
+    with torch.cuda.device(q.device):
+        out = torch.empty(nd, dtype=torch.float32, device=q.device)
+        _lib.check(lib.qst_rerank_scores(q.data_ptr(), d.data_ptr(), off.data_ptr(), nq, nd, dim, _mode(mode), out.data_ptr(),
+                                         _lib.current_stream_ptr()), "qst_rerank_scores")
+    return out
+
+
+def rerank_metrics(scores: torch.Tensor, offsets, num_pos, k: int = 10):
+    """Reciprocal rank within k, average precision and NDCG within k of every group, and their means (libqst
+    qst_rerank_metrics; include/qst.h states the counts and the tie rule: among equal scores the earlier document ranks
+    first). scores fp32 [nd] on the HIP device, the larger the better; the first num_pos[g] documents of group g are its
+    positives. Returns (per_query float64 [nq, 3] = {rr, ap, ndcg}, out float64 [5] = {mean rr, mean ap, mean ndcg,
+    non-finite scores, invalid groups}), both on the device. Host offsets / num_pos are checked first (ValueError names the
+    first bad group); device tensors are passed through and out[4] counts the groups the kernel could not use. Current
+    stream, nothing copied to the host."""
+    from . import _lib
+    scores = torch.as_tensor(scores)
+    if scores.dim() != 1 or int(k) < 1:
+        raise ValueError(f"rerank_metrics: scores {tuple(scores.shape)} must be [nd] and k = {k} at least 1")
+    nd = scores.numel()
+    off, pos, nq = _rerank_groups("rerank_metrics", offsets, num_pos, nd)
+    if not scores.is_cuda:
+        raise _lib.QstError("rerank_metrics runs on the HIP device: pass a CUDA tensor (there is no CPU fallback)")
+    lib = _lib.load()
+    s = scores.to(torch.float32).contiguous()
+    off = off.to(s.device, torch.int64).contiguous()
+    pos = pos.to(s.device, torch.int32).contiguous()
+    with torch.cuda.device(s.device):
+        per_query = torch.empty(nq, 3, dtype=torch.float64, device=s.device)
+        out = torch.empty(5, dtype=torch.float64, device=s.device)
+        nbytes = int(lib.qst_rerank_workspace_bytes(nq, nd))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+        _lib.check(lib.qst_rerank_metrics(s.data_ptr(), off.data_ptr(), pos.data_ptr(), nq, nd, min(int(k), RERANK_MAX),
+                                          per_query.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes,
+                                          _lib.current_stream_ptr()), "qst_rerank_metrics")
+    return per_query, out
 
 
 # corpus rows per chunk of the streaming top-k where the caller does not say: the score block is
