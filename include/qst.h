@@ -155,10 +155,10 @@ int qst_encoder_set_ffn_chain(qst_encoder* enc, int mask);
 int qst_encoder_set_ln_fusion(qst_encoder* enc, int mode);
 /* The pooling head of this handle (ST models.Pooling): an OR of the QST_POOL_* bits below, concatenated in the fixed order
  * cls, max, mean, mean_sqrt_len, weightedmean (include/qst_kernels.h: qst_pool_fwd has the exact semantics). 0 or
- * QST_POOL_MEAN = mean pooling, the state of a new handle and the only head before version 101: qst_pool_norm_fwd/bwd,
- * unchanged. Any other mode runs qst_pool_fwd/bwd. out_emb / grad_emb of qst_encoder_forward / _backward* are then
- * [nseq, D] with D = qst_encoder_embedding_dim(); qst_encoder_saved_bytes grows by the pre-normalize D-vector and, with
- * max, an int32 [nseq, H] argmax. A training forward records its mode with the arena: a backward of a handle set to
+ * QST_POOL_MEAN = mean pooling, the state of a new handle. Every mode runs qst_pool_fwd/bwd, the only pooling entry
+ * points since version 114. out_emb / grad_emb of qst_encoder_forward / _backward* are [nseq, D] with
+ * D = qst_encoder_embedding_dim(); qst_encoder_saved_bytes grows by the pre-normalize D-vector and, with max, an int32
+ * [nseq, H] argmax. A training forward records its mode with the arena: a backward of a handle set to
  * another mode is refused (QST_ERR_BAD_ARG). */
 #define QST_POOL_CLS 1
 #define QST_POOL_MAX 2

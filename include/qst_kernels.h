@@ -273,12 +273,6 @@ int qst_position_ids(const int64_t* ids, int nseq, int L, int arch, int pad_id, 
 int qst_forward_prologue(const int64_t* ids, int nseq, int L, int arch, int pad_id, int32_t* pos_ids,
                          uint32_t* drop_state, uint32_t* drop_snapshot, void* stream);
 
-/* ST Pooling(mean) + optional Normalize. tok f32 [nseq,L,H]; pooled f32 [nseq,H] (pre-normalize, saved). */
-int qst_pool_norm_fwd(const float* tok, const int64_t* mask, int nseq, int L, int H, int normalize,
-                      float* emb, float* pooled, void* stream);
-int qst_pool_norm_bwd(const float* demb, const float* pooled, const int64_t* mask, int nseq, int L, int H,
-                      int normalize, float* dtok, void* stream);
-
 /* Every ST 2.2.2 Pooling mode + optional Normalize, one launch per direction for any combination. mode = an OR of the
  * QST_POOL_* bits; the enabled blocks are concatenated in the fixed order cls, max, mean, mean_sqrt_len, weightedmean
  * (whatever order a caller names them in): emb / pooled f32 [nseq, D], D = (number of bits) * H, normalised over all of
@@ -287,7 +281,8 @@ int qst_pool_norm_bwd(const float* demb, const float* pooled, const int64_t* mas
  * 1e-9); mean_sqrt_len = sum(m x) / sqrt(max(sum m, 1e-9)); weightedmean = sum(m w x) / max(sum(m w), 1e-9), w_t = t + 1.
  * pooled (pre-normalize) and argmax (int32 [nseq, H], the token row of each column's max; -1 = none) are what the
  * backward reads; both may be NULL in an inference call. The backward writes every row of dtok f32 [nseq, L, H]; argmax
- * is needed when mode has QST_POOL_MAX. H even, <= 1024; L <= 512. */
+ * is needed when mode has QST_POOL_MAX. H even, <= 1024; L <= 512. mode == QST_POOL_MEAN, the default head, launches the
+ * mean-only instantiation of the same two kernels (csrc/rowops.hip). */
 #define QST_POOL_CLS 1
 #define QST_POOL_MAX 2
 #define QST_POOL_MEAN 4

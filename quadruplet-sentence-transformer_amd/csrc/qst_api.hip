@@ -15,7 +15,7 @@
 static thread_local int g_last_hip_error = 0;
 extern "C" int qst_set_hip_error(int code) { g_last_hip_error = code; return code; }
 extern "C" int qst_last_hip_error(void) { return g_last_hip_error; }
-extern "C" int qst_version(void) { return 113; }
+extern "C" int qst_version(void) { return 114; }
 
 extern "C" const char* qst_strerror(int s) {
     switch (s) {
@@ -160,7 +160,7 @@ struct qst_encoder {
     // that wait on the LDS-DMA stream, and stores and DMAs retire through one in-order counter.
     int ffn_chain = 1;
     int ln_fusion = 0;      // qst_encoder_set_ln_fusion: 0 = by size, 1 = wherever a fused kernel exists, 2 = never
-    int pool = QST_POOL_MEAN;   // qst_encoder_set_pooling: QST_POOL_* bits; mean alone runs the original pool_norm kernels
+    int pool = QST_POOL_MEAN;   // qst_encoder_set_pooling: QST_POOL_* bits
 };
 
 extern "C" int64_t qst_arena_elems(const qst_config* cfg) { return cfg_ok(cfg) ? build_layout(cfg).total : QST_ERR_BAD_ARG; }
@@ -613,18 +613,15 @@ struct Pass {
         q.drop = probs(QST_DROP_SITE_PROBS(l));
         return q;
     }
-    // pooling (+ normalisation) into out_emb, and the token states into out_tok when asked for. Mean pooling alone runs
-    // the original kernel pair (pool_norm_fwd/bwd), every other head qst_pool_fwd/bwd.
+    // pooling (+ normalisation) into out_emb, and the token states into out_tok when asked for
     int tail(const float* x, size_t pooled, size_t argmax, float* out_emb, float* out_tok) const {
-        if (e->pool == QST_POOL_MEAN) QST_TRY(qst_pool_norm_fwd(x, mask, nseq, L, H, c.normalize, out_emb, F(pooled), st));
-        else QST_TRY(qst_pool_fwd(x, mask, nseq, L, H, e->pool, c.normalize, out_emb, F(pooled), argmax_at(argmax), st));
+        QST_TRY(qst_pool_fwd(x, mask, nseq, L, H, e->pool, c.normalize, out_emb, F(pooled), argmax_at(argmax), st));
         if (out_tok) QST_HIP_CHECK(hipMemcpyAsync(out_tok, x, (size_t)M * H * 4, hipMemcpyDeviceToDevice, st));
         return QST_OK;
     }
 
     int32_t* argmax_at(size_t off) const { return (e->pool & QST_POOL_MAX) ? (int32_t*)(sv + off) : nullptr; }
     int head_bwd(const float* grad_emb, size_t pooled, size_t argmax, float* dtok) const {
-        if (e->pool == QST_POOL_MEAN) return qst_pool_norm_bwd(grad_emb, F(pooled), mask, nseq, L, H, c.normalize, dtok, st);
         return qst_pool_bwd(grad_emb, F(pooled), argmax_at(argmax), mask, nseq, L, H, e->pool, c.normalize, dtok, st);
     }
     // a backward over an arena that a training forward of ANOTHER pooling head filled is refused (its saved vector and

@@ -380,157 +380,23 @@ __global__ void position_ids_kernel(const int64_t* ids, int nseq, int L, int arc
     }
 }
 
-// mean pool + normalise (sentence-transformers Pooling(mean) + Normalize). One workgroup of 8 waves per sequence. A wave takes every 8th token row, a lane two columns per 64 (8-byte accesses,
-// a row is read / written by whole 512-byte wave instructions); rows of padding are not read. (One thread per column
-// walking the L rows one after the other, 256 threads per sequence, ran at 2.2 TB/s.)
-constexpr int POOL_WAVES = 8, POOL_VPL = 8;                // H <= 1024
-__global__ __launch_bounds__(64 * POOL_WAVES) void pool_norm_fwd_kernel(const float* tok, const int64_t* mask, int L, int H,
-                                                                        int normalize, float* emb, float* pooled) {
-    __shared__ float red[POOL_WAVES];
-    __shared__ float msk[512];
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // [POOL_WAVES][H] floats
-    float* part = (float*)smem;
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nv = H >> 1;
-    for (int t = tid; t < L; t += 64 * POOL_WAVES) msk[t] = (float)mask[(size_t)s * L + t];
-    __syncthreads();
-    float cnt = 0.f;
-    for (int t = 0; t < L; ++t) cnt += msk[t];
-    const float inv = 1.0f / fmaxf(cnt, 1e-9f);
-    f32x2 acc[POOL_VPL];
-#pragma unroll
-    for (int i = 0; i < POOL_VPL; ++i) { acc[i][0] = 0.f; acc[i][1] = 0.f; }
-    // four rows of this wave in flight at a time
-    for (int t0 = wave; t0 < L; t0 += 4 * POOL_WAVES) {
-        f32x2 v[4][POOL_VPL];
-        float m[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int t = t0 + u * POOL_WAVES;
-            m[u] = t < L ? msk[t] : 0.f;
-            const float* row = tok + ((size_t)s * L + (t < L ? t : 0)) * H;
-#pragma unroll
-            for (int i = 0; i < POOL_VPL; ++i) {
-                const int c = lane + 64 * i;
-                v[u][i][0] = v[u][i][1] = 0.f;
-                if (c < nv && m[u] != 0.f) v[u][i] = *(const f32x2*)(row + 2 * c);       // (m: uniform)
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int i = 0; i < POOL_VPL; ++i) { acc[i][0] += v[u][i][0] * m[u]; acc[i][1] += v[u][i][1] * m[u]; }
-    }
-#pragma unroll
-    for (int i = 0; i < POOL_VPL; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv) *(f32x2*)(part + wave * H + 2 * c) = acc[i];
-    }
-    __syncthreads();
-    float sq = 0.f;
-    float e[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int c = tid + 64 * POOL_WAVES * k;
-        e[k] = 0.f;
-        if (c < H) {
-            float a = 0.f;
-#pragma unroll
-            for (int w = 0; w < POOL_WAVES; ++w) a += part[w * H + c];
-            e[k] = a * inv;
-            sq += e[k] * e[k];
-            if (pooled) pooled[(size_t)s * H + c] = e[k];
-        }
-    }
-    sq = wave_sum(sq);
-    if (lane == 0) red[wave] = sq;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < POOL_WAVES; ++w) tot += red[w];
-    const float nrm = sqrtf(tot);
-    const float sc = normalize ? 1.0f / fmaxf(nrm, 1e-12f) : 1.0f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int c = tid + 64 * POOL_WAVES * k;
-        if (c < H) emb[(size_t)s * H + c] = e[k] * sc;
-    }
-}
-
-__global__ __launch_bounds__(64 * POOL_WAVES) void pool_norm_bwd_kernel(const float* demb, const float* pooled, const int64_t* mask,
-                                                                        int L, int H, int normalize, float* dtok) {
-    __shared__ float red[2 * POOL_WAVES];
-    __shared__ float msk[512];
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // [H] floats: the gradient of the mean row
-    float* dps = (float*)smem;
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nv = H >> 1;
-    for (int t = tid; t < L; t += 64 * POOL_WAVES) msk[t] = (float)mask[(size_t)s * L + t];
-    __syncthreads();
-    float cnt = 0.f;
-    for (int t = 0; t < L; ++t) cnt += msk[t];
-    const float inv = 1.0f / fmaxf(cnt, 1e-9f);
-    float e[2], g[2];
-    float sq = 0.f, dot = 0.f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int c = tid + 64 * POOL_WAVES * k;
-        e[k] = g[k] = 0.f;
-        if (c < H) {
-            e[k] = pooled[(size_t)s * H + c];
-            g[k] = demb[(size_t)s * H + c];
-            sq += e[k] * e[k];
-            dot += e[k] * g[k];
-        }
-    }
-    sq = wave_sum(sq); dot = wave_sum(dot);
-    if (lane == 0) { red[wave] = sq; red[POOL_WAVES + wave] = dot; }
-    __syncthreads();
-    sq = 0.f; dot = 0.f;
-#pragma unroll
-    for (int w = 0; w < POOL_WAVES; ++w) { sq += red[w]; dot += red[POOL_WAVES + w]; }
-    const float nrm = sqrtf(sq);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int c = tid + 64 * POOL_WAVES * k;
-        if (c < H) {
-            float dp = g[k];
-            if (normalize) {
-                // y = e / max(n, eps): dy/de = (I - e e^T / n^2) / n for n > eps, I/eps otherwise
-                if (nrm > 1e-12f) dp = (g[k] - e[k] * dot / sq) / nrm;
-                else dp = g[k] / 1e-12f;
-            }
-            dps[c] = dp * inv;
-        }
-    }
-    __syncthreads();
-    f32x2 d[POOL_VPL];
-#pragma unroll
-    for (int i = 0; i < POOL_VPL; ++i) {
-        const int c = lane + 64 * i;
-        d[i][0] = d[i][1] = 0.f;
-        if (c < nv) d[i] = *(const f32x2*)(dps + 2 * c);
-    }
-    for (int t = wave; t < L; t += POOL_WAVES) {
-        const float m = msk[t];
-        float* row = dtok + ((size_t)s * L + t) * H;
-#pragma unroll
-        for (int i = 0; i < POOL_VPL; ++i) {
-            const int c = lane + 64 * i;
-            if (c < nv) { f32x2 o; o[0] = d[i][0] * m; o[1] = d[i][1] * m; *(f32x2*)(row + 2 * c) = o; }
-        }
-    }
-}
-
 // Every pooling mode of sentence-transformers 2.2.2 models.Pooling + optional Normalize, one launch for any combination:
 // the enabled blocks of [cls | max | mean | mean_sqrt_len | weightedmean] (QST_POOL_* bits 0..4, always in this order)
-// are concatenated into a D = k * H vector per sequence and normalised over all of D. Layout of pool_norm_fwd_kernel:
-// one workgroup of 8 waves per sequence, a wave takes every 8th token row, a lane two columns per 64 (8-byte accesses);
-// rows of padding are not read, and a head without max / mean-like blocks (pure cls) reads row 0 only. The cross-wave
-// reduction goes through [8][H] floats of LDS, one quantity after the other (max adds [8][H] ints for its argmax). The
-// D-vector never goes through LDS: each thread keeps its two columns of every block in registers, so D = 5 * 1024 needs
-// no more LDS than H = 1024 (64 KiB with max).
+// are concatenated into a D = k * H vector per sequence and normalised over all of D. One workgroup of 8 waves per
+// sequence, a wave takes every 8th token row, a lane two columns per 64 (8-byte accesses, a row is read / written by whole
+// 512-byte wave instructions); rows of padding are not read, and a head without max / mean-like blocks (pure cls) reads
+// row 0 only. (One thread per column walking the L rows one after the other, 256 threads per sequence, ran at 2.2 TB/s.)
+// The cross-wave reduction goes through [8][H] floats of LDS, one quantity after the other (max adds [8][H] ints for its
+// argmax). The D-vector never goes through LDS: each thread keeps its two columns of every block in registers, so
+// D = 5 * 1024 needs no more LDS than H = 1024 (64 KiB with max).
 // max: padding rows count as -1e9 (ST fills them in place before torch.max), so a sequence with no valid token pools to
 // -1e9 in every column and its argmax is -1 (no gradient); ties go to the LOWEST token index.
+// MEAN_ONLY: the instantiation for mode == QST_POOL_MEAN, the default head and the hot one. `mode` is a constant there, and
+// what the other heads add (weighted sum, max, cls, the barriers between the staged quantities) is compiled out rather than
+// multiplied by zero, so it keeps one accumulator set and one pass through LDS: acc += v * m, e = a * inv.
+constexpr int POOL_WAVES = 8, POOL_VPL = 8;                // H <= 1024
 constexpr int POOL_NMODES = 5;
+template <bool MEAN_ONLY>
 __global__ __launch_bounds__(64 * POOL_WAVES) void pool_fwd_kernel(const float* tok, const int64_t* mask, int L, int H, int mode,
                                                                    int normalize, float* emb, float* pooled, int32_t* argmax) {
     __shared__ float red[POOL_WAVES];
@@ -539,6 +405,7 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_fwd_kernel(const float* 
     float* part = (float*)smem;
     int* pidx = (int*)(part + POOL_WAVES * H);
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nv = H >> 1;
+    if constexpr (MEAN_ONLY) mode = QST_POOL_MEAN;
     const bool want_max = (mode & QST_POOL_MAX) != 0;
     const bool want_sum = (mode & (QST_POOL_MEAN | QST_POOL_MEAN_SQRT)) != 0, want_w = (mode & QST_POOL_WMEAN) != 0;
     const bool rows = want_max || want_sum || want_w;                // (uniform)
@@ -550,8 +417,10 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_fwd_kernel(const float* 
         for (int t = 0; t < L; ++t) {
             const float m = msk[t];
             cnt += m;
-            wcnt += m * (float)(t + 1);
-            npad += m == 0.f ? 1.f : 0.f;
+            if constexpr (!MEAN_ONLY) {
+                wcnt += m * (float)(t + 1);
+                npad += m == 0.f ? 1.f : 0.f;
+            }
         }
     }
     const float mx0 = npad > 0.f ? -1e9f : -INFINITY;
@@ -587,11 +456,13 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_fwd_kernel(const float* 
 #pragma unroll
                 for (int i = 0; i < POOL_VPL; ++i) {
                     as[i] += v[u][i] * m[u];
-                    aw[i] += v[u][i] * wt;
-                    if (want_max && m[u] != 0.f) {
+                    if constexpr (!MEAN_ONLY) {
+                        aw[i] += v[u][i] * wt;
+                        if (want_max && m[u] != 0.f) {
 #pragma unroll
-                        for (int h = 0; h < 2; ++h)
-                            if (v[u][i][h] > mx[i][h]) { mx[i][h] = v[u][i][h]; ix[i][h] = t; }
+                            for (int h = 0; h < 2; ++h)
+                                if (v[u][i][h] > mx[i][h]) { mx[i][h] = v[u][i][h]; ix[i][h] = t; }
+                        }
                     }
                 }
             }
@@ -626,8 +497,11 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_fwd_kernel(const float* 
         colsum(sm);
         const float inv = 1.0f / fmaxf(cnt, 1e-9f), rs = sqrtf(fmaxf(cnt, 1e-9f));
 #pragma unroll
-        for (int k = 0; k < 2; ++k) { e[2][k] = sm[k] * inv; e[3][k] = sm[k] / rs; }
-        __syncthreads();
+        for (int k = 0; k < 2; ++k) {
+            e[2][k] = sm[k] * inv;
+            if constexpr (!MEAN_ONLY) e[3][k] = sm[k] / rs;
+        }
+        if constexpr (!MEAN_ONLY) __syncthreads();             // (part is staged again below)
     }
     if (want_w) {
         stage(aw);
@@ -715,6 +589,10 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_fwd_kernel(const float* 
 // row t = m_t * (a + (t + 1) * b) [+ d(cls) on row 0] [+ d(max) in the columns whose argmax is t], with
 // a = d(mean) / count + d(mean_sqrt_len) / sqrt(count) and b = d(weightedmean) / sum(m * w). Rows that receive nothing
 // (padding, and every row of a pure-cls head but row 0) are written as zeros.
+// MEAN_ONLY (mode == QST_POOL_MEAN): a = d(mean) / count is all there is, so only ga exists in LDS ([H] floats, not 5 [H])
+// and a row is a * m_t; b, d(cls), d(max) and the argmax are compiled out (what is staged through LDS cannot be folded away
+// by making `mode` a constant alone).
+template <bool MEAN_ONLY>
 __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(const float* demb, const float* pooled, const int32_t* argmax,
                                                                    const int64_t* mask, int L, int H, int mode, int normalize,
                                                                    float* dtok) {
@@ -727,11 +605,15 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(const float* 
     float* gm = gc + H;
     int* am = (int*)(gm + H);
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nv = H >> 1;
+    if constexpr (MEAN_ONLY) mode = QST_POOL_MEAN;
     const bool want_max = (mode & QST_POOL_MAX) != 0, want_cls = (mode & QST_POOL_CLS) != 0;
     for (int t = tid; t < L; t += 64 * POOL_WAVES) msk[t] = (float)mask[(size_t)s * L + t];
     __syncthreads();
     float cnt = 0.f, wcnt = 0.f;
-    for (int t = 0; t < L; ++t) { cnt += msk[t]; wcnt += msk[t] * (float)(t + 1); }
+    for (int t = 0; t < L; ++t) {
+        cnt += msk[t];
+        if constexpr (!MEAN_ONLY) wcnt += msk[t] * (float)(t + 1);
+    }
     const int D = __popc(mode & 31) * H;
     float e[POOL_NMODES][2], g[POOL_NMODES][2];
     float sq = 0.f, dot = 0.f;
@@ -775,11 +657,15 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(const float* 
                 }
                 if (!(mode & (1 << j))) dp[j] = 0.f;
             }
-            ga[c] = dp[2] * inv + dp[3] / rs;
-            gb[c] = dp[4] / wd;
-            gc[c] = dp[0];
-            gm[c] = dp[1];
-            am[c] = want_max ? argmax[(size_t)s * H + c] : -1;
+            if constexpr (MEAN_ONLY) {
+                ga[c] = dp[2] * inv;
+            } else {
+                ga[c] = dp[2] * inv + dp[3] / rs;
+                gb[c] = dp[4] / wd;
+                gc[c] = dp[0];
+                gm[c] = dp[1];
+                am[c] = want_max ? argmax[(size_t)s * H + c] : -1;
+            }
         }
     }
     __syncthreads();
@@ -792,8 +678,10 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(const float* 
         ai[i][0] = ai[i][1] = -1;
         if (c < nv) {
             a[i] = *(const f32x2*)(ga + 2 * c);
-            b[i] = *(const f32x2*)(gb + 2 * c);
-            if (want_max) { mg[i] = *(const f32x2*)(gm + 2 * c); ai[i][0] = am[2 * c]; ai[i][1] = am[2 * c + 1]; }
+            if constexpr (!MEAN_ONLY) {
+                b[i] = *(const f32x2*)(gb + 2 * c);
+                if (want_max) { mg[i] = *(const f32x2*)(gm + 2 * c); ai[i][0] = am[2 * c]; ai[i][1] = am[2 * c + 1]; }
+            }
         }
     }
     for (int t = wave; t < L; t += POOL_WAVES) {
@@ -803,11 +691,16 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(const float* 
         for (int i = 0; i < POOL_VPL; ++i) {
             const int c = lane + 64 * i;
             if (c < nv) {
-                f32x2 r = a[i] * m + b[i] * wt;
-                if (want_cls && t == 0) r += *(const f32x2*)(gc + 2 * c);
-                if (want_max) {
-                    if (ai[i][0] == t) r[0] += mg[i][0];
-                    if (ai[i][1] == t) r[1] += mg[i][1];
+                f32x2 r;
+                if constexpr (MEAN_ONLY) {
+                    r = a[i] * m;
+                } else {
+                    r = a[i] * m + b[i] * wt;
+                    if (want_cls && t == 0) r += *(const f32x2*)(gc + 2 * c);
+                    if (want_max) {
+                        if (ai[i][0] == t) r[0] += mg[i][0];
+                        if (ai[i][1] == t) r[1] += mg[i][1];
+                    }
                 }
                 *(f32x2*)(row + 2 * c) = r;
             }
@@ -1138,47 +1031,31 @@ extern "C" int qst_forward_prologue(const int64_t* ids, int nseq, int L, int arc
     return QST_OK;
 }
 
-extern "C" int qst_pool_norm_fwd(const float* tok, const int64_t* mask, int nseq, int L, int H, int normalize,
-                                 float* emb, float* pooled, void* stream) {
-    if (!tok || !mask || !emb || nseq <= 0 || L <= 0 || H <= 0) return QST_ERR_BAD_ARG;
+// What both pooling entry points check before a launch; `ptrs`: every pointer the call needs is there.
+static int pool_check(bool ptrs, int nseq, int L, int H, int mode) {
+    if (!ptrs || nseq <= 0 || L <= 0 || H <= 0 || mode <= 0 || mode > QST_POOL_ALL) return QST_ERR_BAD_ARG;
     if (L > 512 || H > 1024) return QST_ERR_UNSUPPORTED;
     if (H & 1) return QST_ERR_UNSUPPORTED;
-    pool_norm_fwd_kernel<<<nseq, 64 * POOL_WAVES, (size_t)POOL_WAVES * H * sizeof(float), (hipStream_t)stream>>>(tok, mask, L, H, normalize,
-                                                                                                           emb, pooled);
-    QST_LAUNCH_CHECK();
-    return QST_OK;
-}
-
-extern "C" int qst_pool_norm_bwd(const float* demb, const float* pooled, const int64_t* mask, int nseq, int L, int H,
-                                 int normalize, float* dtok, void* stream) {
-    if (!demb || !pooled || !mask || !dtok || nseq <= 0 || L <= 0 || H <= 0) return QST_ERR_BAD_ARG;
-    if (L > 512 || H > 1024) return QST_ERR_UNSUPPORTED;
-    if (H & 1) return QST_ERR_UNSUPPORTED;
-    pool_norm_bwd_kernel<<<nseq, 64 * POOL_WAVES, (size_t)H * sizeof(float), (hipStream_t)stream>>>(demb, pooled, mask, L, H, normalize, dtok);
-    QST_LAUNCH_CHECK();
     return QST_OK;
 }
 
 extern "C" int qst_pool_fwd(const float* tok, const int64_t* mask, int nseq, int L, int H, int mode, int normalize,
                             float* emb, float* pooled, int32_t* argmax, void* stream) {
-    if (!tok || !mask || !emb || nseq <= 0 || L <= 0 || H <= 0 || mode <= 0 || mode > QST_POOL_ALL) return QST_ERR_BAD_ARG;
-    if (L > 512 || H > 1024) return QST_ERR_UNSUPPORTED;
-    if (H & 1) return QST_ERR_UNSUPPORTED;
+    if (const int rc = pool_check(tok && mask && emb, nseq, L, H, mode)) return rc;
     const size_t lds = (size_t)POOL_WAVES * H * ((mode & QST_POOL_MAX) ? sizeof(float) + sizeof(int) : sizeof(float));
-    pool_fwd_kernel<<<nseq, 64 * POOL_WAVES, lds, (hipStream_t)stream>>>(tok, mask, L, H, mode, normalize, emb, pooled, argmax);
+    auto kernel = mode == QST_POOL_MEAN ? pool_fwd_kernel<true> : pool_fwd_kernel<false>;
+    kernel<<<nseq, 64 * POOL_WAVES, lds, (hipStream_t)stream>>>(tok, mask, L, H, mode, normalize, emb, pooled, argmax);
     QST_LAUNCH_CHECK();
     return QST_OK;
 }
 
 extern "C" int qst_pool_bwd(const float* demb, const float* pooled, const int32_t* argmax, const int64_t* mask, int nseq, int L,
                             int H, int mode, int normalize, float* dtok, void* stream) {
-    if (!demb || !pooled || !mask || !dtok || nseq <= 0 || L <= 0 || H <= 0 || mode <= 0 || mode > QST_POOL_ALL)
-        return QST_ERR_BAD_ARG;
-    if ((mode & QST_POOL_MAX) && !argmax) return QST_ERR_BAD_ARG;
-    if (L > 512 || H > 1024) return QST_ERR_UNSUPPORTED;
-    if (H & 1) return QST_ERR_UNSUPPORTED;
-    pool_bwd_kernel<<<nseq, 64 * POOL_WAVES, (size_t)5 * H * sizeof(float), (hipStream_t)stream>>>(demb, pooled, argmax, mask, L, H,
-                                                                                                     mode, normalize, dtok);
+    if (const int rc = pool_check(demb && pooled && mask && dtok && (argmax || !(mode & QST_POOL_MAX)), nseq, L, H, mode)) return rc;
+    const bool mean_only = mode == QST_POOL_MEAN;
+    auto kernel = mean_only ? pool_bwd_kernel<true> : pool_bwd_kernel<false>;
+    kernel<<<nseq, 64 * POOL_WAVES, (size_t)(mean_only ? 1 : 5) * H * sizeof(float), (hipStream_t)stream>>>(demb, pooled, argmax, mask, L,
+                                                                                                         H, mode, normalize, dtok);
     QST_LAUNCH_CHECK();
     return QST_OK;
 }

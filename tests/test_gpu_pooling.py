@@ -1,6 +1,7 @@
 """GPU: the pooling heads of sentence-transformers 2.2.2 (cls, max, mean, mean_sqrt_len, weightedmean, concatenated in
-that order) -- qst_pool_fwd/bwd against a torch restatement of models.Pooling.forward, the mean head's old kernel pair
-untouched, the encoder against the HF token states, training through every path, and the public surface."""
+that order) -- qst_pool_fwd/bwd against a torch restatement of models.Pooling.forward and, bit for bit, against digests
+recorded before the mean head's own kernel pair was folded into them, the encoder against the HF token states, training
+through every path, and the public surface."""
 import json
 import os
 from dataclasses import replace
@@ -18,6 +19,7 @@ from quadruplet_sentence_transformer_amd.synthetic import synthetic_params, synt
 from quadruplet_sentence_transformer_amd.trainer import QuadrupletTrainer, warmup_linear_lr
 from oracle import torch_ref as R
 from kernel_helpers import lib, quad_batch  # noqa: F401
+import pool_digest_cases as P
 
 pytestmark = pytest.mark.gpu
 
@@ -121,36 +123,33 @@ def test_max_ties_go_to_the_lowest_token_index(lib):
             assert col[r] == demb[s, c] and int((col != 0).sum()) == 1
 
 
-def test_mean_head_on_the_new_kernels_agrees_with_the_old_pair(lib):
-    gen = torch.Generator().manual_seed(2)
-    for H, L in ((384, 128), (1024, 512)):
-        for normalize in (False, True):
-            n = 8
-            tok = torch.randn(n, L, H, generator=gen).cuda()
-            mask = ragged_mask(n, L, gen).cuda()
-            e_old, p_old = torch.empty(n, H, device="cuda"), torch.empty(n, H, device="cuda")
-            _lib.check(lib.qst_pool_norm_fwd(tok.data_ptr(), mask.data_ptr(), n, L, H, int(normalize), e_old.data_ptr(),
-                                             p_old.data_ptr(), _lib.current_stream_ptr()))
-            emb, pooled, argmax = pool_fwd(lib, tok, mask, 4, normalize, H)
-            torch.testing.assert_close(emb, e_old, rtol=1e-5, atol=1e-6)
-            demb = torch.randn(n, H, generator=gen).cuda()
-            d_old = torch.empty(n, L, H, device="cuda")
-            _lib.check(lib.qst_pool_norm_bwd(demb.data_ptr(), p_old.data_ptr(), mask.data_ptr(), n, L, H, int(normalize),
-                                             d_old.data_ptr(), _lib.current_stream_ptr()))
-            torch.testing.assert_close(pool_bwd(lib, demb, pooled, argmax, mask, 4, normalize, L, H), d_old, rtol=1e-5, atol=1e-6)
+def test_every_head_reproduces_the_digests_of_the_two_pair_kernels(lib, golden_dir):
+    """Bitwise, on every head: each case of tests/pool_digest_cases.py run on the tree's library gives the SHA-256 of emb,
+    pooled, argmax and dtok that tests/golden/pool_digests.json recorded (tools/pool_digest.py) on the library of the commit
+    named there, whose mean head still ran its own kernel pair."""
+    want = json.load(open(os.path.join(golden_dir, "pool_digests.json")))["cases"]
+    assert sorted(want) == sorted(P.case_name(*c) for c in P.CASES), "the recorded cases are not the cases of pool_digest_cases.py"
+    different = []
+    for case in P.CASES:
+        name = P.case_name(*case)
+        got = P.run_case(lib.qst_pool_fwd, lib.qst_pool_bwd, *case, stream=_lib.current_stream_ptr())
+        assert got["inputs"] == want[name]["inputs"], f"{name}: inputs changed, not the kernel"
+        different += [f"{name}: {k}" for k in want[name] if got.get(k) != want[name][k]]
+        assert set(got) == set(want[name]), name
+    assert not different, different
 
 
 @pytest.mark.parametrize("precision", ["bf16", "bf16x3"])
 def test_default_encoder_still_runs_the_old_mean_kernel(lib, precision):
-    """An encoder left at the default head: its embeddings are BITWISE those of qst_pool_norm_fwd on its own token states."""
+    """An encoder left at the default head: its embeddings are BITWISE those of qst_pool_fwd(mode = QST_POOL_MEAN) on its own
+    token states."""
     cfg = PRESETS["tiny-bert"]
     enc = HipEncoder(cfg, device="cuda:0")
     enc.load_arena(synthetic_params(cfg, seed=14, std=0.05))
     ids, mask, types = [torch.from_numpy(x).cuda().view(-1, 64) for x in synthetic_quadruplets(cfg, 3, 64, seed=14, ragged=True)]
     emb, tok, _ = enc.forward(ids, mask, types, want_tokens=True, precision=precision)
     n, L, H = tok.shape
-    ref = torch.empty(n, H, device="cuda")
-    _lib.check(lib.qst_pool_norm_fwd(tok.data_ptr(), mask.data_ptr(), n, L, H, 1, ref.data_ptr(), None, _lib.current_stream_ptr()))
+    ref, _, _ = pool_fwd(lib, tok, mask, pooling_mask("mean"), True, H)
     assert torch.equal(emb, ref)
     assert lib.qst_encoder_embedding_dim(enc.handle) == H
 

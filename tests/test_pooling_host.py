@@ -140,7 +140,9 @@ def test_pooling_entry_points_are_exported_and_bound():
     lib = _lib.load()
     for name in ("qst_encoder_set_pooling", "qst_encoder_embedding_dim", "qst_pool_fwd", "qst_pool_bwd"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.qst_version() >= 101
+    assert lib.qst_version() >= 114
+    for name in ("qst_pool_norm_fwd", "qst_pool_norm_bwd"):        # version 114: one kernel pair, one pair of entry points
+        assert not hasattr(lib, name) and name not in _lib.SIGNATURES
     # argument checks come before any launch: no device needed
     assert lib.qst_encoder_set_pooling(None, 1) == -1 and lib.qst_encoder_embedding_dim(None) == -1
     assert lib.qst_pool_fwd(None, None, 1, 32, 64, 1, 1, None, None, None, None) == -1
