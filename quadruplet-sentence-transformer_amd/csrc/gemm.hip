@@ -389,8 +389,13 @@ __device__ __forceinline__ void nt_epilogue(const QstGemmArgs& g, f32x16 (&acc)[
                 const int m = m_base + i * 32 + row;
                 const int n = n_base + c8 * 8;
                 const u32x4 z = {0u, 0u, 0u, 0u};
-                if (EPI == QST_EPI_GELU_BWD)
-                    av[t] = (m < g.M && n < g.N) ? ld_stream((const u32x4*)((const op16*)g.aux + (size_t)m * g.ldc + n)) : z;
+                if (EPI == QST_EPI_GELU_BWD) {
+                    // (an N % 8 == 4 tail reads its 8 bytes only: 16 would end behind a dense aux in the last row)
+                    const op16* ap = (const op16*)g.aux + (size_t)m * g.ldc + n;
+                    av[t] = z;
+                    if (m < g.M && n + 8 <= g.N) av[t] = ld_stream((const u32x4*)ap);
+                    else if (m < g.M && n < g.N) { const u32x2 h2 = ld_stream((const u32x2*)ap); av[t][0] = h2[0]; av[t][1] = h2[1]; }
+                }
             }
 #pragma unroll
             for (int j = 0; j < 3; ++j)
