@@ -153,6 +153,20 @@ int qst_encoder_set_ffn_chain(qst_encoder* enc, int mask);
  * 128 x 384 where only that gives two: H = 768 from 32,768 token rows),
  * 1 = wherever such a kernel exists, 2 = never. Same results to fp32 summation order. */
 int qst_encoder_set_ln_fusion(qst_encoder* enc, int mode);
+/* How the 16-bit backward (every precision but QST_PREC_BF16X3) issues the weight gradients: 0 = the library's choice
+ * (qst_wgrad_pairs_rule), 1 = one grouped launch per layer, 2 = one launch for two neighbouring layers wherever a call allows
+ * it. A call pairs when it covers at least two layers and carries neither QST_BWD_SKIP_WGRAD nor QST_BWD_WGRAD_ONLY: pairs are
+ * formed from the call's lowest layer up -- (1, 0), (3, 2), (5, 4); with an odd count the top layer keeps its own launch --
+ * and a pair's launch is issued where the lower layer's was. Calls of one layer run as with 1. Where the handle may pair,
+ * qst_encoder_bwd_workspace_bytes grows by a second set of the four tensors a launch reads (bf16 [M, H], [M, H], [M, I] and
+ * [M, 3H]): set the mode BEFORE sizing the workspace. Same products; the fp32 partial sums are grouped differently. */
+int qst_encoder_set_wgrad_pairs(qst_encoder* enc, int mode);
+/* Host only, no device needed. The library's choice for cfg at M token rows (1 = pairs): at least two layers, M >= 8,192,
+ * and at least one but fewer than two 192 x 192 tiles per workgroup in a layer's own launch (32 <= qst_wgrad_tiles(cfg, M, 1)
+ * < 64: MiniLM's 48). DESIGN.md finding 48. */
+int qst_wgrad_pairs_rule(const qst_config* cfg, int M);
+/* Host only: the output tiles of the weight-gradient launch of `layers` (1 or 2) layers of cfg. */
+int qst_wgrad_tiles(const qst_config* cfg, int M, int layers);
 /* The pooling head of this handle (ST models.Pooling): an OR of the QST_POOL_* bits below, concatenated in the fixed order
  * cls, max, mean, mean_sqrt_len, weightedmean (include/qst_kernels.h: qst_pool_fwd has the exact semantics). 0 or
  * QST_POOL_MEAN = mean pooling, the state of a new handle. Every mode runs qst_pool_fwd/bwd, the only pooling entry

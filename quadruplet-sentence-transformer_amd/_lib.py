@@ -188,6 +188,9 @@ SIGNATURES = {
     "qst_encoder_set_dropout": (C.c_int, [vp, C.c_float, C.c_float, vp]),
     "qst_encoder_set_ffn_chain": (C.c_int, [vp, C.c_int]),
     "qst_encoder_set_ln_fusion": (C.c_int, [vp, C.c_int]),
+    "qst_encoder_set_wgrad_pairs": (C.c_int, [vp, C.c_int]),
+    "qst_wgrad_pairs_rule": (C.c_int, [C.POINTER(QstConfig), C.c_int]),
+    "qst_wgrad_tiles": (C.c_int, [C.POINTER(QstConfig), C.c_int, C.c_int]),
     "qst_encoder_set_pooling": (C.c_int, [vp, C.c_int]),
     "qst_encoder_embedding_dim": (C.c_int, [vp]),
     "qst_transpose_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),

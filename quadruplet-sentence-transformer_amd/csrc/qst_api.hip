@@ -15,7 +15,7 @@
 static thread_local int g_last_hip_error = 0;
 extern "C" int qst_set_hip_error(int code) { g_last_hip_error = code; return code; }
 extern "C" int qst_last_hip_error(void) { return g_last_hip_error; }
-extern "C" int qst_version(void) { return 114; }
+extern "C" int qst_version(void) { return 115; }
 
 extern "C" const char* qst_strerror(int s) {
     switch (s) {
@@ -160,6 +160,7 @@ struct qst_encoder {
     // that wait on the LDS-DMA stream, and stores and DMAs retire through one in-order counter.
     int ffn_chain = 1;
     int ln_fusion = 0;      // qst_encoder_set_ln_fusion: 0 = by size, 1 = wherever a fused kernel exists, 2 = never
+    int wgrad_pairs = 0;    // qst_encoder_set_wgrad_pairs: 0 = by shape (wgrad_pair_rule), 1 = one launch per layer, 2 = pairs
     int pool = QST_POOL_MEAN;   // qst_encoder_set_pooling: QST_POOL_* bits
 };
 
@@ -417,20 +418,66 @@ MxOperands plan_mx_train_operands(const qst_config& c, int nseq, int L, size_t b
     return t;
 }
 
-struct BwdPlan { size_t dxa, dxb, ds, dsb, dsb1, du, dctx, dqkv, drel, lnred, lnred_stride, delta, total; };
-BwdPlan plan_bwd(const qst_config& c, int nseq, int L) {
+// dsb / dsb1 / du / dqkv are the dY operands of a layer's weight-gradient launch. pair: a second set of the four behind
+// everything else (no other offset moves), so that two neighbouring layers' operands are alive at once and one launch can
+// take both layers (Pass::backward_op16); without it [1] is [0].
+struct BwdPlan { size_t dxa, dxb, ds, dsb[2], dsb1[2], du[2], dctx, dqkv[2], drel, lnred, lnred_stride, delta, total; };
+BwdPlan plan_bwd(const qst_config& c, int nseq, int L, bool pair) {
     BwdPlan p;
     const size_t M = (size_t)nseq * L, H = c.hidden_size, I = c.intermediate_size, A = c.num_heads;
     Bump take;
-    p.dxa = take(M * H * 4); p.dxb = take(M * H * 4); p.ds = take(M * H * 4); p.dsb = take(M * H * 2);
-    p.dsb1 = take(M * H * 2);
-    p.du = take(M * I * 2); p.dctx = take(M * H * 2); p.dqkv = take(M * 3 * H * 2);
+    p.dxa = take(M * H * 4); p.dxb = take(M * H * 4); p.ds = take(M * H * 4); p.dsb[0] = take(M * H * 2);
+    p.dsb1[0] = take(M * H * 2);
+    p.du[0] = take(M * I * 2); p.dctx = take(M * H * 2); p.dqkv[0] = take(M * 3 * H * 2);
     p.drel = (c.arch == QST_ARCH_MPNET) ? take(A * (size_t)2 * L * 4) : 0;
     p.lnred_stride = (qst_ln_bwd_scratch_bytes((int)M, (int)H) + 255) / 256 * 256;
     p.lnred = take(p.lnred_stride * (size_t)(2 * c.num_layers + 1));
     p.delta = take((size_t)nseq * A * L * 4);
+    p.dsb[1] = pair ? take(M * H * 2) : p.dsb[0];
+    p.dsb1[1] = pair ? take(M * H * 2) : p.dsb1[0];
+    p.du[1] = pair ? take(M * I * 2) : p.du[0];
+    p.dqkv[1] = pair ? take(M * 3 * H * 2) : p.dqkv[0];
     p.total = take.off;
     return p;
+}
+
+// The shapes of a layer's four weight-gradient products -- dW2 [H, I], dW1 [I, H], dWo [H, H], dWqkv [3H, H], each the
+// reduction of dY[M, N]^T . X[M, K] over the M token rows -- as problems at .. at + 3 of a grouped launch.
+void wgrad_shapes(QstTnGroup& g, int at, int M, int H, int I) {
+    const int nk[4][2] = {{H, I}, {I, H}, {H, H}, {3 * H, H}};
+    for (int i = 0; i < 4; ++i) {
+        QstGemmArgs& q = g.prob[at + i];
+        q.M = M; q.N = nk[i][0]; q.K = nk[i][1];
+        q.lda = q.N; q.ldb = q.K; q.ldc = q.K;
+    }
+}
+// ... and the output tiles of such a launch: what the 32 workgroups of an M-range share out
+constexpr int kTnTile = 192;        // the tile of gemm_tn_group_kernel (csrc/gemm.hip: TT)
+int wgrad_tiles(const qst_config& c, int M, int layers) {
+    QstTnGroup g{};
+    g.nprob = 4 * layers;
+    for (int k = 0; k < layers; ++k) wgrad_shapes(g, 4 * k, M, c.hidden_size, c.intermediate_size);
+    int tiles = 0;
+    for (int i = 0; i < g.nprob; ++i)
+        tiles += ((g.prob[i].N + kTnTile - 1) / kTnTile) * ((g.prob[i].K + kTnTile - 1) / kTnTile);
+    return tiles;
+}
+static_assert(QST_TN_MAX_PROB >= 8, "a launch takes the weight gradients of two layers");
+
+// The library's choice of qst_encoder_set_wgrad_pairs (mode 0). The weight gradients of two neighbouring layers go into ONE
+// launch where a layer alone hands the 32 workgroups of an M-range one to two 192 x 192 tiles each (MiniLM: 48 tiles, one
+// whole tile and half of a leftover one per workgroup; the pair: 96 = three whole tiles, no leftover piece, a quarter fewer
+// flushes, one start-up): measured in the step at M = 8,192 / 16,384 / 32,768, -3.8% / -1.4% / -0.6% (DESIGN.md finding 48).
+// From two tiles per workgroup on (H = 768: 192 tiles) a layer keeps its own launch -- the pair gains 1% per launch there and
+// loses 0.4% in the step, where the QKV dgrad no longer follows a launch that has just read its operand. Fewer than 8,192
+// rows, and layers of fewer tiles than workgroups, were not measured and stay as they were.
+constexpr int kWgradPairMinRows = 8192;
+bool wgrad_pair_rule(const qst_config& c, int M) {
+    const int tiles = wgrad_tiles(c, M, 1);
+    return c.num_layers >= 2 && M >= kWgradPairMinRows && tiles >= 32 && tiles < 2 * 32;
+}
+bool wgrad_pairing(const qst_config& c, int M, int mode) {
+    return c.num_layers >= 2 && (mode == 2 || (mode == 0 && wgrad_pair_rule(c, M)));
 }
 
 int shape_ok(const qst_encoder* e, int nseq, int L) {
@@ -454,6 +501,19 @@ extern "C" int qst_encoder_set_ln_fusion(qst_encoder* e, int mode) {
     if (!e || mode < 0 || mode > 2) return QST_ERR_BAD_ARG;
     e->ln_fusion = mode;
     return QST_OK;
+}
+extern "C" int qst_encoder_set_wgrad_pairs(qst_encoder* e, int mode) {
+    if (!e || mode < 0 || mode > 2) return QST_ERR_BAD_ARG;
+    e->wgrad_pairs = mode;
+    return QST_OK;
+}
+extern "C" int qst_wgrad_pairs_rule(const qst_config* cfg, int M) {
+    if (!cfg_ok(cfg) || M <= 0) return QST_ERR_BAD_ARG;
+    return wgrad_pair_rule(*cfg, M) ? 1 : 0;
+}
+extern "C" int qst_wgrad_tiles(const qst_config* cfg, int M, int layers) {
+    if (!cfg_ok(cfg) || M <= 0 || layers < 1 || layers > 2) return QST_ERR_BAD_ARG;
+    return wgrad_tiles(*cfg, M, layers);
 }
 extern "C" int qst_encoder_set_pooling(qst_encoder* e, int mode) {
     if (!e || mode < 0 || mode > QST_POOL_ALL) return QST_ERR_BAD_ARG;
@@ -485,7 +545,7 @@ extern "C" size_t qst_encoder_saved_bytes(const qst_encoder* e, int nseq, int L,
 extern "C" size_t qst_encoder_bwd_workspace_bytes(const qst_encoder* e, int nseq, int L) {
     if (shape_ok(e, nseq, L) != QST_OK) return 0;
     if (e->cfg.precision == QST_PREC_BF16X3) return plan_x3_bwd(e->cfg, nseq, L).total;
-    return plan_bwd(e->cfg, nseq, L).total;
+    return plan_bwd(e->cfg, nseq, L, wgrad_pairing(e->cfg, nseq * L, e->wgrad_pairs)).total;
 }
 
 namespace {
@@ -986,19 +1046,23 @@ int Pass::backward_x3(const float* grad_emb, size_t saved_bytes, size_t workspac
 int Pass::backward_op16(const void* shadow, const float* grad_emb, size_t saved_bytes, size_t workspace_bytes, int flags,
                         int layer_hi, int layer_lo) {
     const ActPlan p = plan_acts(c, nseq, L, true, e->pool);
-    const BwdPlan w = plan_bwd(c, nseq, L);
+    // Two neighbouring layers' weight gradients in one launch (wgrad_pair_rule): only a call that covers both layers and
+    // issues its launches itself can do that; the staged calls of the data-parallel path (one layer each, layer 0's launch
+    // postponed) run as before, inside the first set of dY tensors. The workspace is sized by the handle alone.
+    const BwdPlan w = plan_bwd(c, nseq, L, wgrad_pairing(c, M, e->wgrad_pairs));
     if (saved_bytes < p.total || workspace_bytes < w.total) return QST_ERR_WORKSPACE;
+    const bool pairing = w.dsb[1] != w.dsb[0] && layer_hi - layer_lo >= 2 && !(flags & (QST_BWD_SKIP_WGRAD | QST_BWD_WGRAD_ONLY));
     const uint16_t* sh = (const uint16_t*)shadow;
     auto WT = [&](int seg) { return sh + lay.segs[seg].shadow_off + qst_align_up(lay.segs[seg].numel, kAlign); };
 
     float* dxa = (float*)(ws + w.dxa);
     float* dxb = (float*)(ws + w.dxb);
     float* ds = (float*)(ws + w.ds);
-    void* dsb = ws + w.dsb;
-    void* dsb1 = ws + w.dsb1;
-    void* du = ws + w.du;
     void* dctx = ws + w.dctx;
-    void* dqkv = ws + w.dqkv;
+    // The dY set of layer l. A pairing call alternates from its top layer down, so that a layer's tensors outlive the layer
+    // below it; the top layer of every call -- whose dsb the QKV dgrad of the call above has written in fused mode -- and
+    // every layer of a call that does not pair use set 0.
+    auto set_of = [&](int l) { return pairing && l >= layer_lo ? (layer_hi - 1 - l) & 1 : 0; };
     // LayerNorm gamma/beta gradients: every ln_bwd of this call writes per-block partials into its own slot; one
     // batched launch at the end reduces them all (13 small launches per step -> 1-7)
     QstLnReduceBatch lnb{};
@@ -1026,30 +1090,35 @@ int Pass::backward_op16(const void* shadow, const float* grad_emb, size_t saved_
         if (flags & QST_BWD_HEAD) QST_HIP_CHECK(hipMemsetAsync(drel, 0, (size_t)A * 2 * L * 4, st));
     }
     if (flags & QST_BWD_HEAD) QST_TRY(head_bwd(grad_emb, p.pooled, p.argmax, dxa));
-    // all four weight gradients (+ bias gradients) of a layer in one grouped launch
-    auto wgrad = [&](int l) -> int {
-        const LayerAct& a = p.layers[l];
-        const int b = lay.layer0[l];
-        const void* xin_b = (l == 0) ? (const void*)(sv + p.x0b) : (const void*)(sv + p.layers[l - 1].xb);
+    // all four weight gradients (+ bias gradients) of a layer in one grouped launch, or those of layers l_up and l_up - 1
+    auto wgrad = [&](int l_up, int layers) -> int {
         QstTnGroup grp{};
-        grp.nprob = 4;
+        grp.nprob = 4 * layers;
         grp.splits = 0;
-        auto set = [&](int i, const void* dY, int N, const void* X, int K, int wseg, int bseg) {
-            QstGemmArgs& q = grp.prob[i];
-            q.A = dY; q.B = X; q.C = G(wseg); q.colsum = G(bseg); q.M = M; q.N = N; q.K = K;
-            q.lda = N; q.ldb = K; q.ldc = K;
-        };
-        set(0, dsb, H, sv + a.hact, I, b + W_2, b + B_2);          // dW2 [H, I]
-        set(1, du, I, sv + a.y1b, H, b + W_1, b + B_1);            // dW1 [I, H]
-        set(2, dsb1, H, sv + a.ctx, H, b + W_O, b + B_O);          // dWo [H, H]
-        set(3, dqkv, 3 * H, xin_b, H, b + W_QKV, b + B_QKV);       // dWqkv [3H, H]
+        for (int k = 0; k < layers; ++k) {
+            const int l = l_up - k, s = set_of(l);
+            const LayerAct& a = p.layers[l];
+            const int b = lay.layer0[l];
+            const void* xin_b = (l == 0) ? (const void*)(sv + p.x0b) : (const void*)(sv + p.layers[l - 1].xb);
+            wgrad_shapes(grp, 4 * k, M, H, I);
+            auto set = [&](int i, const void* dY, const void* X, int wseg, int bseg) {
+                QstGemmArgs& q = grp.prob[4 * k + i];
+                q.A = dY; q.B = X; q.C = G(wseg); q.colsum = G(bseg);
+            };
+            set(0, ws + w.dsb[s], sv + a.hact, b + W_2, b + B_2);          // dW2 [H, I]
+            set(1, ws + w.du[s], sv + a.y1b, b + W_1, b + B_1);            // dW1 [I, H]
+            set(2, ws + w.dsb1[s], sv + a.ctx, b + W_O, b + B_O);          // dWo [H, H]
+            set(3, ws + w.dqkv[s], xin_b, b + W_QKV, b + B_QKV);           // dWqkv [3H, H]
+        }
         return ops.gemm_tn_group(&grp, st);
     };
     // the dY tensors of exactly one layer live in the workspace: the one whose stage ran with QST_BWD_SKIP_WGRAD
-    if (flags & QST_BWD_WGRAD_ONLY) return wgrad(layer_lo);
+    if (flags & QST_BWD_WGRAD_ONLY) return wgrad(layer_lo, 1);
     for (int l = layer_hi - 1; l >= layer_lo; --l) {
         const LayerAct& a = p.layers[l];
         const int b = lay.layer0[l];
+        const int s = set_of(l);
+        void *dsb = ws + w.dsb[s], *dsb1 = ws + w.dsb1[s], *du = ws + w.du[s], *dqkv = ws + w.dqkv[s];
         // LN2 -> ds2 (fp32 for the residual path, bf16 for the GEMMs). Fused mode: only the top layer runs it as a
         // row kernel; below, (ds, dsb) were written by the QKV dgrad of layer l+1.
         if (!fuse_ln || l == c.num_layers - 1)
@@ -1084,15 +1153,21 @@ int Pass::backward_op16(const void* shadow, const float* grad_emb, size_t saved_
         QstAttnDesc q = attn(l, sv + a.qkv, sv + a.ctx, F(a.lse));
         q.dctx = dctx; q.dqkv = dqkv; q.drel = drel; q.delta_scratch = (float*)(ws + w.delta);
         QST_TRY(ops.attention_bwd_ex(&q, st));
-        if (!(flags & QST_BWD_SKIP_WGRAD)) QST_TRY(wgrad(l));
+        // pairs from the bottom of the call: (lo + 1, lo), (lo + 3, lo + 2), ...; with an odd count the top layer is alone.
+        // A pair's launch sits where the lower layer's did; the upper layer's operands wait in their own set.
+        if (!pairing) {
+            if (!(flags & QST_BWD_SKIP_WGRAD)) QST_TRY(wgrad(l, 1));
+        } else if (((l - layer_lo) & 1) == 0) {
+            QST_TRY(wgrad(l + 1 < layer_hi ? l + 1 : l, l + 1 < layer_hi ? 2 : 1));
+        }
         // QKV projection dgrad + residual: dx_in = dqkv . Wqkv + ds1. Fused mode: followed in the same kernel by the
         // backward of the LayerNorm that produced this layer's input (LN2 of layer l-1, or the embedding LayerNorm)
         if (fuse_ln && l > 0) {
             const LayerAct& lo = p.layers[l - 1];
             const int bl = lay.layer0[l - 1];
-            // dsb = d(FFN-2 output of layer l-1)
+            // dsb of layer l - 1 = d(FFN-2 output of layer l-1)
             QST_TRY(nt_ln(dqkv, WT(b + W_QKV), ds, 3 * H, 1,
-                          {.C2 = dsb, .resid = ds1, .drop = hidden(QST_DROP_SITE_FFN_OUT(l - 1)), .drop_where = 2},
+                          {.C2 = ws + w.dsb[set_of(l - 1)], .resid = ds1, .drop = hidden(QST_DROP_SITE_FFN_OUT(l - 1)), .drop_where = 2},
                           {.gamma = P(bl + LN2_G), .xhat = sv + lo.xh2, .rstd = F(lo.rs2),
                            .partials = ln_slot(2 * (l - 1) + 1, G(bl + LN2_G), G(bl + LN2_B), fused_rows)}));
         } else if (fuse_ln) {

@@ -100,6 +100,7 @@ class HipEncoder:
         self.dropout_step = 0
         self.drop_state = None
         self.ln_fusion = 0
+        self.wgrad_pairs = 0
         self._live: Dict[str, _Live] = {}       # canonical precision name -> what exists of it; created on first use
         self._record("bf16")
         self.emb_dim = self.lib.qst_encoder_embedding_dim(self.handle)
@@ -130,6 +131,8 @@ class HipEncoder:
                            "qst_encoder_set_dropout")
             if self.ln_fusion:
                 _lib.check(self.lib.qst_encoder_set_ln_fusion(h, self.ln_fusion), "qst_encoder_set_ln_fusion")
+            if self.wgrad_pairs:
+                _lib.check(self.lib.qst_encoder_set_wgrad_pairs(h, self.wgrad_pairs), "qst_encoder_set_wgrad_pairs")
         except Exception:
             self.lib.qst_encoder_destroy(h)
             raise
@@ -238,6 +241,14 @@ class HipEncoder:
         for rec in self._live.values():
             _lib.check(self.lib.qst_encoder_set_ln_fusion(rec.handle, int(mode)), "qst_encoder_set_ln_fusion")
         self.ln_fusion = int(mode)
+
+    def set_wgrad_pairs(self, mode: int) -> None:
+        """How a backward issues the weight gradients (include/qst.h qst_encoder_set_wgrad_pairs): 0 the library's choice
+        (default), 1 one grouped launch per layer, 2 one launch for two neighbouring layers wherever a call covers both.
+        Every precision's handle; the backward workspace of a handle that may pair is larger (bwd_workspace_bytes)."""
+        for rec in self._live.values():
+            _lib.check(self.lib.qst_encoder_set_wgrad_pairs(rec.handle, int(mode)), "qst_encoder_set_wgrad_pairs")
+        self.wgrad_pairs = int(mode)
 
     def set_dropout_step(self, step: int) -> None:
         """Continue the mask stream at `step` training forwards (checkpoint resume)."""
