@@ -1,9 +1,10 @@
 """sentence_transformers.losses: the pair, triplet, in-batch-negatives, batch-mining triplet, distillation and
-softmax-classifier objectives on the HIP path (st_losses.py)."""
+softmax-classifier objectives on the HIP path, and MatryoshkaLoss over them (st_losses.py)."""
 from quadruplet_sentence_transformer_amd.st_losses import (BatchAllTripletLoss, BatchHardSoftMarginTripletLoss,  # noqa: F401
                                                            BatchHardTripletLoss, BatchHardTripletLossDistanceFunction,
                                                            BatchSemiHardTripletLoss, ContrastiveLoss, CosineSimilarityLoss,
-                                                           MarginMSELoss, MSELoss, MultipleNegativesRankingLoss,
+                                                           MarginMSELoss, MatryoshkaLoss, MSELoss,
+                                                           MultipleNegativesRankingLoss,
                                                            MultipleNegativesSymmetricRankingLoss,
                                                            OnlineContrastiveLoss, SiameseDistanceMetric, SoftmaxLoss,
                                                            TripletDistanceMetric, TripletLoss)

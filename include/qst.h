@@ -321,6 +321,31 @@ int qst_mnrl_loss(const float* a, const float* c, int B, int N, int D, int sim, 
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * MatryoshkaLoss over (Symmetric)MultipleNegativesRankingLoss (version 116; csrc/mnrl_nested.hip): the loss above at K nested
+ * prefixes of the embedding in one call. a, c, B, N, D, scale, symmetric as for qst_mnrl_loss. dims and weights are HOST
+ * arrays of K entries: K distinct widths 1 <= d_k <= D in any order, 1 <= K <= 8, and finite weights. For each k
+ *   x_hat_k = F.normalize(x[:, :d_k], p=2, dim=1, eps=1e-12), S_k = scale * a_hat_k c_hat_k^T,
+ *   term_k = the plain or symmetric cross entropy of S_k as qst_mnrl_loss defines it for QST_SCORE_COS
+ * (normalising after truncating makes util.cos_sim and util.dot_score the same scores: there is no sim argument).
+ * out_terms fp32 [K] or NULL receives term_k in the caller's order; out_loss[0] = sum_k w_k term_k, summed in that order.
+ * grad_a [B, D] and grad_c [N, D] are full width: the sum over k of w_k times the gradient through truncation and
+ * normalisation, times *grad_out (device scalar, NULL = 1; it multiplies the finished gradient); the columns from max_k d_k on
+ * are written as exact zeros; a prefix with |x[:d_k]| < 1e-12 follows torch's clamp as in qst_mnrl_loss. Both NULL = forward
+ * only (nothing else is written); exactly one NULL is QST_ERR_BAD_ARG.
+ * K outside 1 .. 8, a width outside 1 .. D or repeated, a weight that is not finite, NULL dims or weights, a workspace smaller
+ * than qst_mnrl_nested_workspace_bytes(B, N, D, K) (0 for a bad shape or K) or not 4-byte aligned, and every bad argument of
+ * qst_mnrl_loss: QST_ERR_BAD_ARG before any launch, nothing written. B * ldS or N * D past 2^31 - 1: QST_ERR_UNSUPPORTED. Any
+ * other shape and any widths are accepted. The number of launches (6 with gradients, 7 symmetric) and of passes over a and c
+ * does not depend on K. No atomics, no host synchronisation, capturable; the same inputs give bit-identical outputs.
+ */
+size_t qst_mnrl_nested_workspace_bytes(int B, int N, int D, int K);
+int qst_mnrl_nested_loss(const float* a, const float* c, int B, int N, int D,
+                         const int32_t* dims, const float* weights, int K,
+                         float scale, int symmetric, float* out_loss, float* out_terms,
+                         const float* grad_out, float* grad_a, float* grad_c,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The batch-mining triplet losses of sentence-transformers 2.2.2 (version 106; csrc/batch_triplet.hip): BatchHardTripletLoss,
  * BatchHardSoftMarginTripletLoss, BatchSemiHardTripletLoss, BatchAllTripletLoss. x fp32 [B, D], rows contiguous; labels
  * int64 [B]. d [B, B] is the distance of every pair of rows: metric QST_METRIC_L2_PLAIN (sqrt(sum_k (x_ik - x_jk)^2); bit-identical

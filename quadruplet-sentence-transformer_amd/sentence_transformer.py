@@ -13,6 +13,7 @@ only as HF-named VIEWS of the arena (so `named_parameters()` and name-based deca
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import logging
 import math
@@ -183,14 +184,18 @@ class _Holder(nn.Module):
 class SentenceTransformer(nn.Module):
     def __init__(self, model_name_or_path: Optional[str] = None, modules=None, device=None,
                  cache_folder: Optional[str] = None, config: Optional[EncoderConfig] = None, seed: int = 14,
-                 allow_random_init: Optional[bool] = None):
+                 allow_random_init: Optional[bool] = None, truncate_dim: Optional[int] = None):
         """model_name_or_path: a local ST/HF model directory, or a model NAME, which is resolved offline the way
         sentence-transformers 2.2.2 resolves it -- `cache_folder` (or $SENTENCE_TRANSFORMERS_HOME), then the Hugging Face
         hub cache. A name with no checkpoint on disk RAISES: fine-tuning or evaluating random weights under a
         pretrained model's name is never what a caller of the reference scripts wants. Random-init weights of a named
         architecture are available on request only: `allow_random_init=True` (or QST_ALLOW_RANDOM_INIT=1), or an
-        explicit `config=`; the `tiny-*` presets are synthetic test architectures and always random-init."""
+        explicit `config=`; the `tiny-*` presets are synthetic test architectures and always random-init.
+        truncate_dim: encode() keeps the first `truncate_dim` columns of every sentence embedding (a model trained with
+        losses.MatryoshkaLoss is cut to one of its widths this way); None = the full width. It is a setting of this
+        object only: save() does not persist it."""
         super().__init__()
+        self.truncate_dim = _checked_truncate_dim(truncate_dim)
         self._model_card_name = model_name_or_path
         arena = None
         tok_dir = None
@@ -302,8 +307,21 @@ class SentenceTransformer(nn.Module):
         return self._modules.get("2")
 
     def get_sentence_embedding_dimension(self) -> int:
+        """The width encode() returns: that of the module chain, or `truncate_dim` while that is set and smaller."""
         dense = self._dense
-        return self.cfg.embedding_dim if dense is None else dense.get_sentence_embedding_dimension()
+        full = self.cfg.embedding_dim if dense is None else dense.get_sentence_embedding_dimension()
+        return full if self.truncate_dim is None else min(full, self.truncate_dim)
+
+    @contextlib.contextmanager
+    def truncate_sentence_embeddings(self, truncate_dim: Optional[int]):
+        """Inside the block encode() -- and with it every evaluator that encodes through it -- returns the first
+        `truncate_dim` columns of the sentence embeddings (None = the full width); the previous setting comes back on exit,
+        also when the block raises. forward(), and so training, is never truncated."""
+        before, self.truncate_dim = self.truncate_dim, _checked_truncate_dim(truncate_dim)
+        try:
+            yield
+        finally:
+            self.truncate_dim = before
 
     def get_max_seq_length(self) -> int:
         return self.max_seq_length
@@ -362,14 +380,17 @@ class SentenceTransformer(nn.Module):
     def encode(self, sentences: Union[str, List[str]], batch_size: int = 32, show_progress_bar: Optional[bool] = None,
                output_value: str = "sentence_embedding", convert_to_numpy: bool = True,
                convert_to_tensor: bool = False, device: Optional[str] = None, normalize_embeddings: bool = False,
-               precision: Optional[str] = None):
+               precision: Optional[str] = None, truncate_dim: Optional[int] = None):
         """precision: None = self.inference_precision; "bf16x3" = embeddings within rtol 1e-3/atol 1e-4 of fp32.
+        truncate_dim: None = self.truncate_dim; the first `truncate_dim` columns of the sentence embedding are kept BEFORE
+        normalize_embeddings is applied (sentence-transformers' order). token_embeddings are not truncated.
         output_value="token_embeddings": per sentence the final token states [n_tokens, H], trimmed to its attention mask's
         length, as ST 2.2.2 returns them (a list; tensors, or numpy arrays with convert_to_numpy)."""
         if output_value not in ("sentence_embedding", "token_embeddings"):
             raise NotImplementedError("output_value is 'sentence_embedding' or 'token_embeddings'")
         if output_value == "token_embeddings":
             return self._encode_tokens(sentences, batch_size, convert_to_numpy and not convert_to_tensor, precision)
+        cut = self.truncate_dim if truncate_dim is None else _checked_truncate_dim(truncate_dim)
         was_training, was_prec = self.training, self.inference_precision
         if precision is not None:
             self.inference_precision = precision
@@ -386,12 +407,18 @@ class SentenceTransformer(nn.Module):
             for start in range(0, len(sorted_s), batch_size):
                 feats = self.tokenize(sorted_s[start:start + batch_size])
                 emb = self.forward(feats)["sentence_embedding"].detach()
+                if cut is not None and cut < emb.shape[1]:
+                    emb = emb[:, :cut]
                 if normalize_embeddings and emb.shape[0] > 0:
                     emb = emb.contiguous()
                     _lib.check(self._enc.lib.qst_normalize_rows(emb.data_ptr(), emb.shape[0], emb.shape[1], emb.data_ptr(),
                                                                 _lib.current_stream_ptr()), "qst_normalize_rows")
                 chunks.append(emb.cpu() if convert_to_numpy else emb)
-        allemb = torch.cat(chunks, 0) if chunks else torch.zeros(0, self.get_sentence_embedding_dimension())
+        if chunks:
+            allemb = torch.cat(chunks, 0)
+        else:
+            with self.truncate_sentence_embeddings(cut):
+                allemb = torch.zeros(0, self.get_sentence_embedding_dimension())
         inv = np.argsort(order)
         allemb = allemb[torch.as_tensor(inv, device=allemb.device)] if len(inv) else allemb
         if convert_to_numpy:
@@ -721,6 +748,8 @@ class SentenceTransformer(nn.Module):
 
     # ---- save / load: ST model-directory layout (modules.json, config.json, model.safetensors, 1_Pooling/...)
     def save(self, path: str, model_name: Optional[str] = None, create_model_card: bool = False, **kwargs):
+        """Writes the model directory. `truncate_dim` is not persisted: a reloaded model returns the full width until it is
+        given the keyword again."""
         if path is None:
             return
         os.makedirs(path, exist_ok=True)
@@ -760,6 +789,14 @@ class SentenceTransformer(nn.Module):
         json.dump(modules, open(os.path.join(path, "modules.json"), "w"), indent=2)
         if self.tokenizer is not None:
             self.tokenizer.save_pretrained(path)
+
+
+def _checked_truncate_dim(truncate_dim):
+    if truncate_dim is None:
+        return None
+    if isinstance(truncate_dim, bool) or int(truncate_dim) != truncate_dim or truncate_dim < 1:
+        raise ValueError(f"truncate_dim is a positive integer or None, {truncate_dim!r} given")
+    return int(truncate_dim)
 
 
 def _collate_labels(labels):

@@ -44,6 +44,11 @@ difference, the squared error and all three gradients are one qst_margin_mse_los
 `SoftmaxLoss` is the one objective here with parameters of its own: an `nn.Linear` classifier on [u, v, |u - v|, u * v] whose
 weights live in a `loss_params.LossParameters`, a flat buffer the fused optimiser step takes next to the arena. Logits, cross
 entropy and all four gradients are csrc/softmax_head.hip (qst_softmax_head_fwd, qst_softmax_ce, qst_softmax_head_bwd).
+
+`MatryoshkaLoss` (sentence-transformers 2.4) wraps one of the objectives above and scores ONE encoder pass at nested prefixes
+of the embedding, each cut, normalised again, weighted and summed. Over the two in-batch-negatives losses all widths are one
+qst_mnrl_nested_loss call forward and one backward (csrc/mnrl_nested.hip), whatever their number up to 8; over any other
+base loss, or with `fused_dims=False`, the base loss's own forward runs once per width on torch slices of the one pass.
 """
 from __future__ import annotations
 
@@ -128,6 +133,34 @@ def mnrl_loss_raw(a, c, sim, scale: float, symmetric: bool, grad_out: Optional[t
                                      out.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grads[0]), _lib.ptr(grads[1]),
                                      ws.data_ptr(), nbytes, _lib.current_stream_ptr()), "qst_mnrl_loss")
     return out, grads
+
+
+NESTED_MAX_DIMS = 8                                # the K qst_mnrl_nested_loss takes
+
+
+def mnrl_nested_loss_raw(a, c, dims, weights, scale: float, symmetric: bool, grad_out: Optional[torch.Tensor] = None,
+                         want_grads: bool = False):
+    """qst_mnrl_nested_loss on contiguous fp32 HIP tensors a [B, D], c [N, D]: the cosine MNRL of the first dims[k] columns,
+    weighted by weights[k] and summed -- (loss [1], terms [K] in the order of `dims`, [grad_a, grad_c] full width or
+    [None, None]). One call whatever K (1 .. 8) is."""
+    lib = _lib.load()
+    if not (a.is_cuda and c.is_cuda):
+        raise _lib.QstError("mnrl_nested_loss_raw runs on the HIP device only (inputs are CPU tensors; no CPU path)")
+    (B, D), N = a.shape, c.shape[0]
+    K = len(dims)
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    terms = torch.empty(max(K, 1), dtype=torch.float32, device=a.device)
+    grads = [torch.empty_like(a), torch.empty_like(c)] if want_grads else [None, None]
+    nbytes = int(lib.qst_mnrl_nested_workspace_bytes(B, N, D, K))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)
+    hd = (_lib.C.c_int32 * max(K, 1))(*[int(d) for d in dims])
+    hw = (_lib.C.c_float * max(K, 1))(*[float(w) for w in weights])
+    with torch.cuda.device(a.device):
+        _lib.check(lib.qst_mnrl_nested_loss(a.data_ptr(), c.data_ptr(), B, N, D, hd, hw, K, float(scale),
+                                            int(bool(symmetric)), out.data_ptr(), terms.data_ptr(), _lib.ptr(grad_out),
+                                            _lib.ptr(grads[0]), _lib.ptr(grads[1]), ws.data_ptr(), nbytes,
+                                            _lib.current_stream_ptr()), "qst_mnrl_nested_loss")
+    return out, terms[:K], grads
 
 
 def batch_triplet_loss_raw(x, labels, kind: int, metric: int, margin: float, grad_out: Optional[torch.Tensor] = None,
@@ -253,6 +286,21 @@ class _MnrlFn(torch.autograd.Function):
         return grads[0].to(ctx.in_dtypes[0]), grads[1].to(ctx.in_dtypes[1]), None, None, None
 
 
+class _MnrlNestedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, c, dims, weights, scale, symmetric):
+        xs = _f32((a, c))
+        out, _, _ = mnrl_nested_loss_raw(xs[0], xs[1], dims, weights, scale, symmetric)
+        ctx.save_for_backward(*xs)
+        ctx.hp, ctx.in_dtypes = (dims, weights, scale, symmetric), (a.dtype, c.dtype)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        _, _, grads = mnrl_nested_loss_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
+        return grads[0].to(ctx.in_dtypes[0]), grads[1].to(ctx.in_dtypes[1]), None, None, None, None
+
+
 class _BatchTripletFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, labels, kind, metric, margin):
@@ -364,6 +412,29 @@ def multiple_negatives_ranking_loss(a: torch.Tensor, c: torch.Tensor, scale: flo
     if not (a.is_cuda and c.is_cuda):
         raise _lib.QstError("multiple_negatives_ranking_loss runs on the HIP device only (inputs are CPU tensors; no CPU path)")
     return _MnrlFn.apply(a, c, sim, float(scale), bool(symmetric))
+
+
+def matryoshka_mnrl_loss(a: torch.Tensor, c: torch.Tensor, dims, weights=None, scale: float = 20.0,
+                         symmetric: bool = False) -> torch.Tensor:
+    """sum_k weights[k] * MNRL(F.normalize(a[:, :dims[k]]), F.normalize(c[:, :dims[k]])) of anchors a [B, D] and candidates
+    c [N, D], N >= B: 1 .. 8 distinct widths in any order, each at most D. One qst_mnrl_nested_loss call, differentiable in
+    a and c (the gradients are full width, zero from the largest width on)."""
+    dims = tuple(int(d) for d in dims)
+    weights = tuple(float(w) for w in (weights if weights is not None else [1.0] * len(dims)))
+    if a.dim() != 2 or c.dim() != 2 or a.shape[1] != c.shape[1] or a.shape[1] < 1:
+        raise ValueError("matryoshka_mnrl_loss: anchors (B, D) and candidates (N, D) must share D >= 1")
+    if a.shape[0] < 1 or c.shape[0] < a.shape[0]:
+        raise ValueError(f"matryoshka_mnrl_loss: {a.shape[0]} anchors need at least as many candidates, {c.shape[0]} given")
+    if not 1 <= len(dims) <= NESTED_MAX_DIMS or len(set(dims)) != len(dims) or len(weights) != len(dims):
+        raise ValueError(f"matryoshka_mnrl_loss: 1 to {NESTED_MAX_DIMS} distinct widths and as many weights, "
+                         f"{list(dims)} and {list(weights)} given")
+    if min(dims) < 1 or max(dims) > a.shape[1]:
+        raise ValueError(f"matryoshka_mnrl_loss: the widths {list(dims)} must lie in 1 .. {a.shape[1]}, the embedding width")
+    if not (scale > 0 and scale < float("inf")):
+        raise ValueError(f"scale must be positive and finite, {scale} given")
+    if not (a.is_cuda and c.is_cuda):
+        raise _lib.QstError("matryoshka_mnrl_loss runs on the HIP device only (inputs are CPU tensors; no CPU path)")
+    return _MnrlNestedFn.apply(a, c, dims, weights, float(scale), bool(symmetric))
 
 
 def batch_triplet_loss(x: torch.Tensor, labels: torch.Tensor, kind: int = BT_HARD, metric: int = METRIC_L2_PLAIN,
@@ -1018,3 +1089,122 @@ class SoftmaxLoss(_TupleLoss):
         if labels is None:
             return [u, v], output
         return self.loss_fct(output, labels.view(-1))
+
+
+# ------------------------------------------------------------------ Matryoshka: one encoder pass scored at nested widths
+def _full_embedding_width(model) -> Optional[int]:
+    """The untruncated width of the model's sentence embeddings (training is never truncated); None for a stand-in that
+    cannot say."""
+    get = getattr(model, "get_sentence_embedding_dimension", None)
+    if get is None:
+        return None
+    cut = getattr(model, "truncate_sentence_embeddings", None)
+    if cut is None:
+        return int(get())
+    with cut(None):
+        return int(get())
+
+
+class MatryoshkaLoss(nn.Module):
+    """sentence-transformers' MatryoshkaLoss: sum_k matryoshka_weights[k] * loss on the embeddings cut to their first
+    matryoshka_dims[k] columns and normalised again, from ONE encoder pass -- the trained model can then be cut to any of
+    those widths (SentenceTransformer(truncate_dim=...), model.truncate_sentence_embeddings(d)).
+
+    `loss` is any of this module's objectives that take their embeddings through `_TupleLoss._embed`. Over
+    `MultipleNegativesRankingLoss` or its symmetric form with `util.cos_sim` or `util.dot_score` (the same scores once the
+    prefix is normalised), up to 8 widths and `fused_dims=True`, all widths are ONE qst_mnrl_nested_loss call
+    (csrc/mnrl_nested.hip) forward and one backward, whatever their number. Anything else -- another base loss, a foreign
+    `similarity_fct`, more than 8 widths, `fused_dims=False` -- runs the base loss's own forward once per width on
+    F.normalize(rep[:, :d], p=2, dim=1) in torch ops, and autograd sums the gradients. `labels` pass through unchanged.
+    `n_dims_per_step` = n with 0 < n < K scores `random.sample` of n of the widths per forward, as sentence-transformers does.
+    `SoftmaxLoss` (its classifier has a fixed input width) and `MSELoss` (the teacher's vectors have the full width) are
+    refused."""
+
+    def __init__(self, model, loss, matryoshka_dims, matryoshka_weights=None, n_dims_per_step: int = -1,
+                 fused_dims: bool = True):
+        super().__init__()
+        if not isinstance(loss, _TupleLoss):
+            raise TypeError(f"MatryoshkaLoss wraps a loss of this package that embeds through _TupleLoss._embed; "
+                            f"{type(loss).__name__} does not derive from _TupleLoss")
+        if isinstance(loss, SoftmaxLoss):
+            raise ValueError("MatryoshkaLoss cannot wrap SoftmaxLoss: its classifier has a fixed input width")
+        if isinstance(loss, MSELoss):
+            raise ValueError("MatryoshkaLoss cannot wrap MSELoss: the teacher's vectors have the full width")
+        dims = [int(d) for d in matryoshka_dims]
+        if not dims:
+            raise ValueError("matryoshka_dims is empty")
+        if len(set(dims)) != len(dims):
+            raise ValueError(f"matryoshka_dims repeats a width: {dims}")
+        if min(dims) < 1:
+            raise ValueError(f"matryoshka_dims must be positive: {dims}")
+        weights = [1.0] * len(dims) if matryoshka_weights is None else [float(w) for w in matryoshka_weights]
+        if len(weights) != len(dims):
+            raise ValueError(f"matryoshka_weights has {len(weights)} entries for {len(dims)} matryoshka_dims")
+        full = _full_embedding_width(model)
+        if full is not None and max(dims) > full:
+            raise ValueError(f"matryoshka_dims {dims}: {max(dims)} is larger than the model's embedding dimension {full}")
+        self.model = model
+        self.loss = loss
+        self.matryoshka_dims = dims
+        self.matryoshka_weights = weights
+        self.n_dims_per_step = n_dims_per_step
+        self.fused_dims = fused_dims
+
+    @property
+    def reduction(self) -> str:
+        red = getattr(self.loss, "reduction", "mean")
+        return red if isinstance(red, str) else "mean"
+
+    def get_config_dict(self):
+        return {"loss": type(self.loss).__name__, "matryoshka_dims": self.matryoshka_dims,
+                "matryoshka_weights": self.matryoshka_weights, "n_dims_per_step": self.n_dims_per_step}
+
+    def _step_indices(self) -> List[int]:
+        idx = range(len(self.matryoshka_dims))
+        if 0 < self.n_dims_per_step < len(idx):
+            import random
+            return random.sample(idx, self.n_dims_per_step)
+        return list(idx)
+
+    def _one_call(self, K: int) -> bool:
+        return self.fused_dims and K <= NESTED_MAX_DIMS and type(self.loss) in (
+            MultipleNegativesRankingLoss, MultipleNegativesSymmetricRankingLoss) and self.loss._kernel_sim() is not None
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor = None) -> torch.Tensor:
+        base = self.loss
+        idx = self._step_indices()
+        dims = [self.matryoshka_dims[i] for i in idx]
+        weights = [self.matryoshka_weights[i] for i in idx]
+        cols = list(sentence_features)
+        if self._one_call(len(dims)):
+            if len(cols) < 2:
+                raise ValueError(f"{type(base).__name__} takes 2 or more text columns per example, {len(cols)} given")
+            reps = base._embed(cols, len(cols))
+            c = reps[1] if len(reps) == 2 else torch.cat(reps[1:], 0)
+            return matryoshka_mnrl_loss(reps[0], c, dims, weights, base.scale, base._symmetric)
+
+        # the base loss's own forward per width, its _embed answering with the cut and renormalised embeddings of one pass
+        embed, state = base._embed, {"reps": None, "d": None}
+        shadowed = base.__dict__.get("_embed")
+
+        def answer(features, k):
+            if state["reps"] is None:
+                state["reps"] = embed(features, k)
+            if any(state["d"] > r.shape[1] for r in state["reps"]):
+                raise ValueError(f"matryoshka width {state['d']} is larger than the embedding width "
+                                 f"{state['reps'][0].shape[1]}")
+            return [torch.nn.functional.normalize(r[:, :state["d"]], p=2, dim=1) for r in state["reps"]]
+
+        base._embed = answer
+        try:
+            total = None
+            for d, w in zip(dims, weights):
+                state["d"] = d
+                term = base(cols, labels) * w
+                total = term if total is None else total + term
+        finally:
+            if shadowed is None:
+                del base._embed
+            else:
+                base._embed = shadowed
+        return total
