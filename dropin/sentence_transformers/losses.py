@@ -1,8 +1,10 @@
-"""sentence_transformers.losses: the pair, triplet, in-batch-negatives, batch-mining triplet, distillation and
-softmax-classifier objectives on the HIP path, and MatryoshkaLoss over them (st_losses.py)."""
-from quadruplet_sentence_transformer_amd.st_losses import (BatchAllTripletLoss, BatchHardSoftMarginTripletLoss,  # noqa: F401
+"""sentence_transformers.losses: the pair, triplet, in-batch-negatives, batch-mining triplet, distillation,
+softmax-classifier and pairwise-ranking (CoSENT, AnglE) objectives on the HIP path, and MatryoshkaLoss over them
+(st_losses.py)."""
+from quadruplet_sentence_transformer_amd.st_losses import (AnglELoss, BatchAllTripletLoss, BatchHardSoftMarginTripletLoss,  # noqa: F401
                                                            BatchHardTripletLoss, BatchHardTripletLossDistanceFunction,
-                                                           BatchSemiHardTripletLoss, ContrastiveLoss, CosineSimilarityLoss,
+                                                           BatchSemiHardTripletLoss, ContrastiveLoss, CoSENTLoss,
+                                                           CosineSimilarityLoss,
                                                            MarginMSELoss, MatryoshkaLoss, MSELoss,
                                                            MultipleNegativesRankingLoss,
                                                            MultipleNegativesSymmetricRankingLoss,

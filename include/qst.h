@@ -376,6 +376,38 @@ int qst_batch_triplet_loss(const float* x, const int64_t* labels, int B, int D, 
                            float* grad_x /* NULL = forward only */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * CoSENTLoss and AnglELoss of sentence-transformers (version 117; csrc/cosent.hip): pairwise ranking of graded pairs. u, v
+ * fp32 [B, D], rows contiguous; labels fp32 [B], the grade of each pair. s_i is the pairwise score of row i:
+ *   QST_PAIRSIM_COS    util.pairwise_cos_sim: sum(u_hat * v_hat), x_hat = F.normalize(x, p=2, dim=1, eps=1e-12); the gradient
+ *                      passes through the normalisation as torch's autograd does (a row with |x| < 1e-12 is x / 1e-12 and
+ *                      its norm passes no gradient, as in qst_mnrl_loss)
+ *   QST_PAIRSIM_ANGLE  util.pairwise_angle_sim, D even: with u = [a, b], v = [c, d] (halves of D / 2)
+ *                      s = |t| / (|u| |v|), t = sum_k a_k (c_k - d_k) + b_k (c_k + d_k); sgn(0) = 0 in the gradient, and
+ *                      there is no epsilon: a zero row gives 0 / 0 = NaN, as upstream
+ * With V = {(i, j) : labels_i < labels_j} and d_ij = scale * (s_i - s_j)
+ *   out_loss[0] = log(1 + sum_V exp(d_ij)),
+ * upstream's logsumexp over the masked B x B differences and a zero, computed around max(0, max_V d_ij). A row whose label
+ * is NaN is in no pair. Without any pair (B = 1, all labels equal) the loss is exactly 0 and the gradients are zeros. A
+ * score that is not finite makes the loss NaN. out_scores fp32 [B] or NULL receives the unscaled s.
+ * grad_u and grad_v [B, D] both NULL = forward only (nothing else is written); exactly one NULL is QST_ERR_BAD_ARG.
+ * grad_out: fp32 [1] on the DEVICE (NULL = 1), read by the kernels -- no host synchronisation, capturable in a HIP graph; it
+ * multiplies the finished gradient. The workspace holds per-row scalars only (six floats a row: there is no B x B buffer);
+ * 3 launches forward, 4 with gradients, whatever B and D are; O(B^2) exps, O(B) per row. No atomics, every reduction in a
+ * fixed order: the same inputs give bit-identical outputs from call to call.
+ * B < 1, D < 1, an odd D with QST_PAIRSIM_ANGLE, a NULL u, v, labels, out_loss or workspace, a workspace smaller than
+ * qst_cosent_workspace_bytes(B, D) or not 16-byte aligned, another sim, a scale that is not finite and positive:
+ * QST_ERR_BAD_ARG before any launch, nothing written. B * D past 2^31 - 1: QST_ERR_UNSUPPORTED. Any other B and D is
+ * accepted (rows in registers up to D = 2048 and streamed beyond, 16 bytes a lane where D % 4 == 0 -- D % 8 == 0 for
+ * QST_PAIRSIM_ANGLE, whose half rows start D / 2 floats apart -- and the pointers are 16-byte aligned, else by element).
+ */
+enum { QST_PAIRSIM_COS = 0, QST_PAIRSIM_ANGLE = 1 };
+size_t qst_cosent_workspace_bytes(int B, int D);
+int qst_cosent_loss(const float* u, const float* v, const float* labels, int B, int D, int sim, float scale,
+                    float* out_loss /* [1] */, float* out_scores /* [B] or NULL */,
+                    const float* grad_out /* device [1], NULL = 1 */, float* grad_u, float* grad_v,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Distillation from a teacher, sentence-transformers 2.2.2 (version 107; csrc/distill.hip): losses.MSELoss and what
  * evaluation.MSEEvaluator scores with, and losses.MarginMSELoss. All tensors fp32, rows contiguous (stride D); any B >= 1 and
  * D >= 1 (16-byte accesses when D % 4 == 0 and the pointers are 16-byte aligned, element by element otherwise; rows are kept

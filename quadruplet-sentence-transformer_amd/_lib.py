@@ -107,6 +107,8 @@ SIGNATURES = {
     "qst_batch_triplet_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "qst_batch_triplet_loss": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, C.c_size_t,
                                          vp]),
+    "qst_cosent_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "qst_cosent_loss": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "qst_embed_mse": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "qst_margin_mse_loss": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "qst_clip_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,

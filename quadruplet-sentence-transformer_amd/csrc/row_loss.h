@@ -1,5 +1,6 @@
-// row_loss.h -- what the row-wise loss kernels (loss.hip, tuple_loss.hip, distill.hip) share around their loops: the row of a
-// wave, the choice of the form a launch takes, the one-workgroup second stage and the cosine's value and gradient scalars.
+// row_loss.h -- what the row-wise loss kernels (loss.hip, tuple_loss.hip, distill.hip, cosent.hip) share around their loops:
+// the row of a wave, the choice of the form a launch takes, the one-workgroup second stage and its block reductions, and the
+// cosine's value and gradient scalars.
 // Row indices, the grid size and the second stage's loop are 64-bit: B may be near INT_MAX.
 #pragma once
 #include <type_traits>
@@ -75,6 +76,21 @@ __global__ __launch_bounds__(1024) void row_sum_kernel(const float* rows, int B,
         if constexpr (std::is_same<T, double>::value) out[0] = (float)(r / k);
         else out[0] = r * k;
     }
+}
+
+// ---- what a one-workgroup second stage of 1024 threads reduces with: the wave tree, then the 16 wave totals through the same
+// tree (part: 16 floats of LDS). A max or min drops NaNs, as fmaxf does.
+enum { OP_SUM = 0, OP_MAX = 1, OP_MIN = 2 };
+template <int OP>
+__device__ __forceinline__ float block_reduce(float v, float* part) {
+    const float id = OP == OP_SUM ? 0.f : (OP == OP_MAX ? -__builtin_inff() : __builtin_inff());
+    v = OP == OP_SUM ? wave_sum(v) : (OP == OP_MAX ? wave_max(v) : -wave_max(-v));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = (threadIdx.x & 63) < 16 ? part[threadIdx.x & 63] : id;
+    r = OP == OP_SUM ? wave_sum(r) : (OP == OP_MAX ? wave_max(r) : -wave_max(-r));
+    __syncthreads();
+    return r;
 }
 
 // ---- cosine of a pair from its dot product and the two norms, and the scalars of its gradient:

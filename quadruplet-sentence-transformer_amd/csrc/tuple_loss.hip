@@ -236,20 +236,7 @@ __global__ __launch_bounds__(256) void tuple_loss_kernel(TupleArgs a) {
     }
 }
 
-// ---- one-workgroup second stages: fixed summation trees, so results are bit-reproducible run to run
-enum { OP_SUM = 0, OP_MAX = 1, OP_MIN = 2 };
-template <int OP>
-__device__ __forceinline__ float block_reduce(float v, float* part) {
-    const float id = OP == OP_SUM ? 0.f : (OP == OP_MAX ? -__builtin_inff() : __builtin_inff());
-    v = OP == OP_SUM ? wave_sum(v) : (OP == OP_MAX ? wave_max(v) : -wave_max(-v));
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = (threadIdx.x & 63) < 16 ? part[threadIdx.x & 63] : id;
-    r = OP == OP_SUM ? wave_sum(r) : (OP == OP_MAX ? wave_max(r) : -wave_max(-r));
-    __syncthreads();
-    return r;
-}
-
+// ---- one-workgroup second stages: fixed summation trees (row_loss.h: block_reduce), so results are bit-reproducible run to run
 // OnlineContrastiveLoss's selection: the thresholds from the other class, then the sum over the selected rows.
 // d: distances [B] followed by the two thresholds this kernel writes for the gradient launch.
 __global__ __launch_bounds__(1024) void online_select_kernel(float* d, const float* labels, int B, float margin, float* out) {

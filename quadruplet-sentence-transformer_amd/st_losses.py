@@ -45,6 +45,11 @@ difference, the squared error and all three gradients are one qst_margin_mse_los
 weights live in a `loss_params.LossParameters`, a flat buffer the fused optimiser step takes next to the arena. Logits, cross
 entropy and all four gradients are csrc/softmax_head.hip (qst_softmax_head_fwd, qst_softmax_ce, qst_softmax_head_bwd).
 
+`CoSENTLoss` and `AnglELoss` (sentence-transformers 2.3 / 2.5) rank graded pairs: two text columns and a float label, the
+loss a logsumexp over every pair of examples whose labels differ. Scores, loss and gradients are one qst_cosent_loss call
+(csrc/cosent.hip) that keeps B scores instead of the B x B differences; `similarity_fct` is recognised by identity
+(`util.pairwise_cos_sim`, `util.pairwise_angle_sim`), any other callable `f(u, v) -> [B]` goes through torch ops.
+
 `MatryoshkaLoss` (sentence-transformers 2.4) wraps one of the objectives above and scores ONE encoder pass at nested prefixes
 of the embedding, each cut, normalised again, weighted and summed. Over the two in-batch-negatives losses all widths are one
 qst_mnrl_nested_loss call forward and one backward (csrc/mnrl_nested.hip), whatever their number up to 8; over any other
@@ -68,6 +73,8 @@ _RED_CODE = {"none": 0, "sum": 1, "mean": 2}
 SCORE_DOT, SCORE_COS = 0, 1                       # QST_SCORE_*: what qst_mnrl_loss takes as `sim`
 _SIM_CODE = {"dot": SCORE_DOT, "cos": SCORE_COS, SCORE_DOT: SCORE_DOT, SCORE_COS: SCORE_COS}
 BT_HARD, BT_HARD_SOFT, BT_SEMIHARD, BT_ALL = range(4)      # QST_BT_*: what qst_batch_triplet_loss takes as `kind`
+PAIRSIM_COS, PAIRSIM_ANGLE = 0, 1                 # QST_PAIRSIM_*: what qst_cosent_loss takes as `sim`
+_PAIRSIM_CODE = {"cos": PAIRSIM_COS, "angle": PAIRSIM_ANGLE, PAIRSIM_COS: PAIRSIM_COS, PAIRSIM_ANGLE: PAIRSIM_ANGLE}
 
 
 # ------------------------------------------------------------------ direct calls (contiguous fp32 HIP tensors [B, D])
@@ -180,6 +187,26 @@ def batch_triplet_loss_raw(x, labels, kind: int, metric: int, margin: float, gra
                                               out.data_ptr(), counts.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grad),
                                               ws.data_ptr(), nbytes, _lib.current_stream_ptr()), "qst_batch_triplet_loss")
     return out, grad, counts
+
+
+def cosent_loss_raw(u, v, labels, sim, scale: float, grad_out: Optional[torch.Tensor] = None, want_grads: bool = False):
+    """qst_cosent_loss on contiguous fp32 HIP tensors u, v [B, D] and labels [B] (sim "cos" / "angle" or PAIRSIM_*): the
+    loss [1], the unscaled pairwise scores [B] and, with want_grads, [grad_u, grad_v] times grad_out (a device scalar;
+    None = 1), else [None, None]."""
+    lib = _lib.load()
+    if not (u.is_cuda and v.is_cuda and labels.is_cuda):
+        raise _lib.QstError("cosent_loss_raw runs on the HIP device only (inputs are CPU tensors; no CPU path)")
+    B, D = u.shape
+    out = torch.empty(1, dtype=torch.float32, device=u.device)
+    scores = torch.empty(B, dtype=torch.float32, device=u.device)
+    grads = _grad_slabs(2, u, want_grads)
+    nbytes = int(lib.qst_cosent_workspace_bytes(B, D))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=u.device)
+    with torch.cuda.device(u.device):
+        _lib.check(lib.qst_cosent_loss(u.data_ptr(), v.data_ptr(), labels.data_ptr(), B, D, _PAIRSIM_CODE[sim], float(scale),
+                                       out.data_ptr(), scores.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grads[0]),
+                                       _lib.ptr(grads[1]), ws.data_ptr(), nbytes, _lib.current_stream_ptr()), "qst_cosent_loss")
+    return out, scores, grads
 
 
 def embed_mse_raw(x, t, grad_out: Optional[torch.Tensor] = None, want_grads: bool = False):
@@ -316,6 +343,22 @@ class _BatchTripletFn(torch.autograd.Function):
         x32, y = ctx.saved_tensors
         _, grad, _ = batch_triplet_loss_raw(x32, y, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
         return grad.to(ctx.in_dtype), None, None, None, None
+
+
+class _CosentFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, v, labels, sim, scale):
+        xs = _f32((u, v))
+        y = labels.detach().to(torch.float32).contiguous().reshape(-1)
+        out, _, _ = cosent_loss_raw(xs[0], xs[1], y, sim, scale)
+        ctx.save_for_backward(xs[0], xs[1], y)
+        ctx.hp, ctx.in_dtypes = (sim, scale), (u.dtype, v.dtype)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        _, _, grads = cosent_loss_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
+        return grads[0].to(ctx.in_dtypes[0]), grads[1].to(ctx.in_dtypes[1]), None, None, None
 
 
 class _EmbedMseFn(torch.autograd.Function):
@@ -458,6 +501,35 @@ def batch_triplet_loss(x: torch.Tensor, labels: torch.Tensor, kind: int = BT_HAR
     _require_rows("batch_triplet_loss", x)
     _require_labels("batch_triplet_loss", labels, x.shape[0])
     return _BatchTripletFn.apply(x, labels, int(kind), int(metric), float(margin))
+
+
+def cosent_loss(u: torch.Tensor, v: torch.Tensor, labels: torch.Tensor, scale: float = 20.0, sim: str = "cos") -> torch.Tensor:
+    """log(1 + sum over the pairs (i, j) with labels[i] < labels[j] of exp(scale * (s_i - s_j))) of two [B, D] HIP tensors and
+    the grades [B], s the pairwise cosine (sim "cos") or util.pairwise_angle_sim (sim "angle", D even). One qst_cosent_loss
+    call, differentiable in u and v; O(B) memory whatever B is."""
+    if sim not in ("cos", "angle"):
+        raise ValueError(f"sim is 'cos' or 'angle', {sim!r} given")
+    if not (scale > 0 and scale < float("inf")):
+        raise ValueError(f"scale must be positive and finite, {scale} given")
+    if u.dim() != 2 or u.shape != v.shape or u.shape[0] < 1 or u.shape[1] < 1:
+        raise ValueError(f"cosent_loss: two (B, D) tensors of one shape, {tuple(u.shape)} and {tuple(v.shape)} given")
+    if sim == "angle" and u.shape[1] % 2:
+        raise ValueError(f"cosent_loss: the angle similarity splits each row into two halves: the width {u.shape[1]} is odd")
+    if labels.numel() != u.shape[0]:
+        raise ValueError(f"cosent_loss: {u.shape[0]} rows but {labels.numel()} labels")
+    _require_rows("cosent_loss", u, v)
+    _require_labels("cosent_loss", labels, u.shape[0])
+    return _CosentFn.apply(u, v, labels, sim, float(scale))
+
+
+def cosent_loss_torch(scores: torch.Tensor, labels: torch.Tensor, scale: float = 20.0) -> torch.Tensor:
+    """The same loss from the pairwise scores [B] as sentence-transformers composes it in torch ops: the B x B differences,
+    the label mask pushed down by 1e12, logsumexp with a zero in front. What CoSENTLoss runs on a foreign similarity_fct."""
+    s = scores * scale
+    s = s[:, None] - s[None, :]
+    mask = (labels[:, None] < labels[None, :]).to(s.dtype)
+    s = s - (1 - mask) * 1e12
+    return torch.logsumexp(torch.cat((torch.zeros(1, dtype=s.dtype, device=s.device), s.view(-1)), dim=0), dim=0)
 
 
 def embed_mse(x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
@@ -880,6 +952,51 @@ class MarginMSELoss(_TupleLoss):
             return margin_mse(q, p, n, labels.view(-1), sim, "mean")
         margin = self.similarity_fct(q, p) - self.similarity_fct(q, n)
         return torch.nn.functional.mse_loss(margin, labels.view(-1).to(margin.dtype))
+
+
+# ------------------------------------------------------------------ pairwise ranking of graded pairs
+class CoSENTLoss(_TupleLoss):
+    """sentence-transformers' CoSENTLoss: log(1 + sum exp(scale * (s_i - s_j))) over the pairs of the batch in which example
+    i has the smaller label, s = similarity_fct(u, v) -- every pair the model ranks against its labels costs, so the loss
+    optimises the order EmbeddingSimilarityEvaluator's Spearman correlation scores. Two text columns and a graded label.
+    With `util.pairwise_cos_sim` (the default) or `util.pairwise_angle_sim`, recognised by identity, scores, loss and both
+    gradients are one qst_cosent_loss call (csrc/cosent.hip) in O(B) memory; any other callable is called as
+    `similarity_fct(u, v) -> [B]` and sentence-transformers' B x B composition runs in torch on its result."""
+    reduction = "mean"
+
+    def __init__(self, model, scale: float = 20.0, similarity_fct=util.pairwise_cos_sim, fused: bool = True):
+        super().__init__(model, fused)
+        self.scale = scale
+        self.similarity_fct = similarity_fct
+
+    def get_config_dict(self):
+        return {"scale": self.scale, "similarity_fct": self.similarity_fct.__name__}
+
+    def _kernel_sim(self) -> Optional[str]:
+        if self.similarity_fct is util.pairwise_cos_sim:
+            return "cos"
+        if self.similarity_fct is util.pairwise_angle_sim:
+            return "angle"
+        return None
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor) -> torch.Tensor:
+        u, v = self._embed(sentence_features, 2)
+        y = labels.view(-1).to(torch.float32)
+        sim = self._kernel_sim()
+        if sim == "angle" and u.shape[1] % 2:
+            raise ValueError(f"{type(self).__name__}: the angle similarity splits each embedding into two halves: the "
+                             f"width {u.shape[1]} is odd")
+        if sim is not None:
+            return cosent_loss(u, v, y, self.scale, sim)
+        return cosent_loss_torch(self.similarity_fct(u, v), y, self.scale)
+
+
+class AnglELoss(CoSENTLoss):
+    """sentence-transformers' AnglELoss: CoSENTLoss on `util.pairwise_angle_sim`, the angle difference of the embeddings read
+    as complex numbers, which does not flatten out near +-1 as the cosine does. The embedding width must be even."""
+
+    def __init__(self, model, scale: float = 20.0, fused: bool = True):
+        super().__init__(model, scale, util.pairwise_angle_sim, fused)
 
 
 # ------------------------------------------------------------------ SoftmaxLoss: a classifier the loss owns and trains

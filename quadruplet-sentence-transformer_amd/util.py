@@ -105,6 +105,28 @@ def pairwise_cos_sim(a, b) -> torch.Tensor:
     return st_losses.pair_metric(a, b, st_losses.METRIC_COS_SIM)
 
 
+def pairwise_angle_sim(x, y) -> torch.Tensor:
+    """sentence_transformers.util.pairwise_angle_sim: the rows of x and y [B, D], D even, read as D / 2 complex numbers
+    (real parts in the first half); the absolute sum of the real and imaginary parts of x / y, each quotient divided by
+    |x| / |y| -- which is |x . [c - d, c + d]| / (|x| |y|) for y = [c, d]. Torch ops with torch's autograd on whatever
+    device the inputs live; no epsilon, a zero row gives NaN as upstream. `losses.CoSENTLoss` recognises this function by
+    identity and runs qst_cosent_loss in its place."""
+    if x.dim() != 2 or x.shape != y.shape:
+        raise ValueError(f"pairwise_angle_sim: two (B, D) tensors of one shape, {tuple(x.shape)} and {tuple(y.shape)} given")
+    if x.shape[1] % 2:
+        raise ValueError(f"pairwise_angle_sim splits each row into two halves: the width {x.shape[1]} is odd")
+    a, b = torch.chunk(x, 2, dim=1)
+    c, d = torch.chunk(y, 2, dim=1)
+    z = torch.sum(c ** 2 + d ** 2, dim=1, keepdim=True)
+    re = (a * c + b * d) / z
+    im = (b * c - a * d) / z
+    dz = torch.sum(a ** 2 + b ** 2, dim=1, keepdim=True) ** 0.5
+    dw = torch.sum(c ** 2 + d ** 2, dim=1, keepdim=True) ** 0.5
+    re = re / (dz / dw)
+    im = im / (dz / dw)
+    return torch.abs(torch.sum(torch.cat((re, im), dim=1), dim=1))
+
+
 # marks this package's own score functions: evaluators route them (and callables that behave like them) to the fused
 # score + top-k kernel instead of materialising the matrix
 cos_sim._qst_mode = SCORE_COS
