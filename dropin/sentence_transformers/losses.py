@@ -1,9 +1,11 @@
 """sentence_transformers.losses: the pair, triplet, in-batch-negatives, batch-mining triplet, distillation,
-softmax-classifier and pairwise-ranking (CoSENT, AnglE) objectives on the HIP path, and MatryoshkaLoss over them
-(st_losses.py)."""
+softmax-classifier and pairwise-ranking (CoSENT, AnglE) objectives on the HIP path, MatryoshkaLoss over them, and the
+GradCache forms of the in-batch-negatives losses (st_losses.py)."""
 from quadruplet_sentence_transformer_amd.st_losses import (AnglELoss, BatchAllTripletLoss, BatchHardSoftMarginTripletLoss,  # noqa: F401
                                                            BatchHardTripletLoss, BatchHardTripletLossDistanceFunction,
-                                                           BatchSemiHardTripletLoss, ContrastiveLoss, CoSENTLoss,
+                                                           BatchSemiHardTripletLoss, CachedMultipleNegativesRankingLoss,
+                                                           CachedMultipleNegativesSymmetricRankingLoss, ContrastiveLoss,
+                                                           CoSENTLoss,
                                                            CosineSimilarityLoss,
                                                            MarginMSELoss, MatryoshkaLoss, MSELoss,
                                                            MultipleNegativesRankingLoss,

@@ -321,6 +321,29 @@ int qst_mnrl_loss(const float* a, const float* c, int B, int N, int D, int sim, 
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * qst_mnrl_loss with no B x N term (version 118; csrc/mnrl_stream.hip): the loss of the large batches of
+ * CachedMultipleNegativesRankingLoss (GradCache). Same mathematics and the same argument contract as qst_mnrl_loss -- cos or
+ * dot, plain or symmetric, the clamp of F.normalize, both gradients NULL = forward only (nothing else is written), exactly one
+ * NULL is QST_ERR_BAD_ARG, grad_out a DEVICE scalar (NULL = 1) that multiplies the finished gradients, every bad argument
+ * refused before any launch with nothing written, no atomics, no host synchronisation, capturable in a HIP graph,
+ * bit-identical from call to call.
+ * The anchors are walked in strips of strip_rows rows: 0 = the library's choice (the largest multiple of 64 whose fp32 score
+ * strip strip_rows x ldS, ldS = N rounded up to 4, fits 64 MiB, at least 64, at most B rounded up to 64), otherwise a positive
+ * multiple of 64; anything else is QST_ERR_BAD_ARG (and a workspace size of 0). Only one strip of scores exists at a time: the
+ * workspace holds strip_rows x ldS floats, per-row and per-column arrays, and the partial sums of one strip's grad_a
+ * (ceil(N / 4096) x strip_rows x D floats when N > 4096) -- linear in B + N at fixed D and strip_rows. The symmetric form
+ * sweeps the strips twice (column statistics first), four products instead of three. All products run on the fp32 matrix
+ * cores (v_mfma_f32_32x32x2_f32: exact fp32).
+ * strip_rows x ldS or N * D past 2^31 - 1: QST_ERR_UNSUPPORTED; B itself has no limit short of int.
+ * Plain form: out_loss and grad_a are bit-identical for every strip_rows; grad_c (summed over the strips) and everything in
+ * the symmetric form (column statistics merged over the strips) may differ between strip_rows by rounding.
+ */
+size_t qst_mnrl_stream_workspace_bytes(int B, int N, int D, int strip_rows);
+int qst_mnrl_stream_loss(const float* a, const float* c, int B, int N, int D, int sim, float scale, int symmetric,
+                         int strip_rows, float* out_loss, const float* grad_out, float* grad_a, float* grad_c,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * MatryoshkaLoss over (Symmetric)MultipleNegativesRankingLoss (version 116; csrc/mnrl_nested.hip): the loss above at K nested
  * prefixes of the embedding in one call. a, c, B, N, D, scale, symmetric as for qst_mnrl_loss. dims and weights are HOST
  * arrays of K entries: K distinct widths 1 <= d_k <= D in any order, 1 <= K <= 8, and finite weights. For each k

@@ -141,11 +141,16 @@ class _EncodeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, model, ids, mask, types, training):
         enc: HipEncoder = model._enc
-        if not training and model.inference_precision != "bf16":
+        # a train()-mode pass without autograd that a second pass WITH autograd will repeat (the cached losses): the same
+        # kernels at the same precision as that second pass, so that both return the same bits
+        first_of_two = training != 1 and model.training and model._no_grad_training_precision
+        if not training and not first_of_two and model.inference_precision != "bf16":
             emb, _, _ = enc.forward(ids, mask, types, training=False, precision=model.inference_precision)
             return emb
         saved = None
-        prec = model.training_precision if training == 1 else "bf16"
+        prec = model.training_precision if training == 1 or first_of_two else "bf16"
+        if first_of_two:
+            training = 2
         if training == 1:
             n, L = ids.shape
             saved = torch.empty(enc.saved_bytes(prec, n, L, True), dtype=torch.uint8, device=enc.device)   # one arena per live graph
@@ -255,6 +260,9 @@ class SentenceTransformer(nn.Module):
         # "bf16", "bf16x3" or "fp8" for forwards that keep a graph (fit(precision=...), reset when fit() returns or raises): the
         # parity path "bf16x3" trains with fp32-class gradients as the reference's fp32 run does (training/main.py:142)
         self.training_precision = "bf16"
+        # off: a train()-mode pass without autograd runs "bf16" (QuadrupletLossEvaluator's validation loss inside fit());
+        # on, inside no_grad_passes_at_training_precision(): it runs at training_precision, as the pass with autograd does
+        self._no_grad_training_precision = False
         self._live_graphs = 0          # training forwards whose backward has not run yet
         self._dp = None                # data-parallel state of a running fit(): {"group", "buckets", "overlap"}
         self._dp_works, self._dp_reduced = [], False
@@ -322,6 +330,17 @@ class SentenceTransformer(nn.Module):
             yield
         finally:
             self.truncate_dim = before
+
+    @contextlib.contextmanager
+    def no_grad_passes_at_training_precision(self):
+        """Inside the block a train()-mode forward under torch.no_grad() runs the training kernels at `training_precision`
+        (with dropout if fit() has it on) instead of "bf16": the first of the two passes of the cached losses, whose
+        embeddings must be the very ones the second pass, with autograd, computes. The previous setting comes back on exit."""
+        before, self._no_grad_training_precision = self._no_grad_training_precision, True
+        try:
+            yield
+        finally:
+            self._no_grad_training_precision = before
 
     def get_max_seq_length(self) -> int:
         return self.max_seq_length
@@ -541,6 +560,12 @@ class SentenceTransformer(nn.Module):
         if data_parallel != "off" and dist.is_available() and dist.is_initialized():
             world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
         dp_mode = (data_parallel or "split_batch") if world > 1 else "off"
+        if world > 1:
+            for lm in loss_models:
+                if getattr(lm, "_replays_mini_batches", False):
+                    raise NotImplementedError(
+                        f"fit(): {type(lm).__name__} is not supported in a data-parallel world of {world}: its backward replays "
+                        f"the batch in mini-batches, and the staged all-reduce would start after the first of them")
         # a loss that owns parameters outside the arena (owned_parameters() -> loss_params.LossParameters: SoftmaxLoss's
         # classifier) is clipped and stepped with the encoder by enc.adamw_step(extra=...); what has no joint entry point refuses here
         owned = [lm.owned_parameters() if hasattr(lm, "owned_parameters") else None for lm in loss_models]

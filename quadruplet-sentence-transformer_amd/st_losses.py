@@ -24,6 +24,11 @@ both gradients in fp32. `similarity_fct` is recognised by identity: `util.cos_si
 rows of its own shard, as with sentence-transformers under DistributedDataParallel: embeddings are not gathered across
 ranks. `data.NoDuplicatesDataLoader` is the loader these losses are meant to be fed by.
 
+`CachedMultipleNegativesRankingLoss` and `CachedMultipleNegativesSymmetricRankingLoss` (GradCache; sentence-transformers
+2.3) are the same two objectives at batches whose activations would not fit: the batch is embedded in mini-batches without
+autograd, loss and embedding gradients come from one qst_mnrl_stream_loss call (csrc/mnrl_stream.hip: strips of anchors, no
+B x N score matrix), and backward() replays the mini-batches with autograd under the same dropout masks. Single process only.
+
 `BatchHardTripletLoss`, `BatchHardSoftMarginTripletLoss`, `BatchSemiHardTripletLoss` and `BatchAllTripletLoss` take ONE text
 column and an integer class label per example, and mine their triplets among the B x B distances of the batch at every
 step: distance matrix, mining, loss and the gradient through the selections are qst_batch_triplet_loss
@@ -139,6 +144,24 @@ def mnrl_loss_raw(a, c, sim, scale: float, symmetric: bool, grad_out: Optional[t
         _lib.check(lib.qst_mnrl_loss(a.data_ptr(), c.data_ptr(), B, N, D, _SIM_CODE[sim], float(scale), int(bool(symmetric)),
                                      out.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grads[0]), _lib.ptr(grads[1]),
                                      ws.data_ptr(), nbytes, _lib.current_stream_ptr()), "qst_mnrl_loss")
+    return out, grads
+
+
+def mnrl_stream_loss_raw(a, c, sim, scale: float, symmetric: bool, strip_rows: int = 0,
+                         grad_out: Optional[torch.Tensor] = None, want_grads: bool = False):
+    """qst_mnrl_stream_loss on contiguous fp32 HIP tensors a [B, D], c [N, D]: mnrl_loss_raw without a B x N score matrix --
+    the anchors are walked in strips of `strip_rows` rows (0 = the library's choice, else a positive multiple of 64)."""
+    lib = _lib.load()
+    (B, D), N = a.shape, c.shape[0]
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    grads = [torch.empty_like(a), torch.empty_like(c)] if want_grads else [None, None]
+    nbytes = int(lib.qst_mnrl_stream_workspace_bytes(B, N, D, int(strip_rows)))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.qst_mnrl_stream_loss(a.data_ptr(), c.data_ptr(), B, N, D, _SIM_CODE[sim], float(scale),
+                                            int(bool(symmetric)), int(strip_rows), out.data_ptr(), _lib.ptr(grad_out),
+                                            _lib.ptr(grads[0]), _lib.ptr(grads[1]), ws.data_ptr(), nbytes,
+                                            _lib.current_stream_ptr()), "qst_mnrl_stream_loss")
     return out, grads
 
 
@@ -313,6 +336,21 @@ class _MnrlFn(torch.autograd.Function):
         return grads[0].to(ctx.in_dtypes[0]), grads[1].to(ctx.in_dtypes[1]), None, None, None
 
 
+class _MnrlStreamFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, c, sim, scale, symmetric, strip_rows):
+        xs = _f32((a, c))
+        out, _ = mnrl_stream_loss_raw(xs[0], xs[1], sim, scale, symmetric, strip_rows)
+        ctx.save_for_backward(*xs)
+        ctx.hp, ctx.in_dtypes = (sim, scale, symmetric, strip_rows), (a.dtype, c.dtype)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        _, grads = mnrl_stream_loss_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
+        return grads[0].to(ctx.in_dtypes[0]), grads[1].to(ctx.in_dtypes[1]), None, None, None, None
+
+
 class _MnrlNestedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, c, dims, weights, scale, symmetric):
@@ -455,6 +493,30 @@ def multiple_negatives_ranking_loss(a: torch.Tensor, c: torch.Tensor, scale: flo
     if not (a.is_cuda and c.is_cuda):
         raise _lib.QstError("multiple_negatives_ranking_loss runs on the HIP device only (inputs are CPU tensors; no CPU path)")
     return _MnrlFn.apply(a, c, sim, float(scale), bool(symmetric))
+
+
+def _check_mnrl_args(name: str, a: torch.Tensor, c: torch.Tensor, scale: float, sim: str) -> None:
+    if sim not in ("cos", "dot"):
+        raise ValueError(f"sim is 'cos' or 'dot', {sim!r} given")
+    if not (scale > 0 and scale < float("inf")):
+        raise ValueError(f"scale must be positive and finite, {scale} given")
+    if a.dim() != 2 or c.dim() != 2 or a.shape[1] != c.shape[1] or a.shape[1] < 1:
+        raise ValueError(f"{name}: anchors (B, D) and candidates (N, D) must share D >= 1")
+    if a.shape[0] < 1 or c.shape[0] < a.shape[0]:
+        raise ValueError(f"{name}: {a.shape[0]} anchors need at least as many candidates, {c.shape[0]} given")
+    if not (a.is_cuda and c.is_cuda):
+        raise _lib.QstError(f"{name} runs on the HIP device only (inputs are CPU tensors; no CPU path)")
+
+
+def multiple_negatives_ranking_loss_stream(a: torch.Tensor, c: torch.Tensor, scale: float = 20.0, sim: str = "cos",
+                                           symmetric: bool = False, strip_rows: int = 0) -> torch.Tensor:
+    """multiple_negatives_ranking_loss for batches whose B x N score matrix should not exist: one qst_mnrl_stream_loss call,
+    which scores `strip_rows` anchors at a time (0 = the library's choice, else a positive multiple of 64) on the fp32 matrix
+    cores. Differentiable in a and c; memory linear in B + N."""
+    if strip_rows < 0 or strip_rows % 64 != 0:
+        raise ValueError(f"strip_rows is 0 or a positive multiple of 64, {strip_rows} given")
+    _check_mnrl_args("multiple_negatives_ranking_loss_stream", a, c, scale, sim)
+    return _MnrlStreamFn.apply(a, c, sim, float(scale), bool(symmetric), int(strip_rows))
 
 
 def matryoshka_mnrl_loss(a: torch.Tensor, c: torch.Tensor, dims, weights=None, scale: float = 20.0,
@@ -777,6 +839,141 @@ class MultipleNegativesRankingLoss(_TupleLoss):
 class MultipleNegativesSymmetricRankingLoss(MultipleNegativesRankingLoss):
     """MultipleNegativesRankingLoss plus the same question asked the other way round -- given positive i, find anchor i among
     the anchors of the batch (the transposed B x B block of the scores) -- and the two halved."""
+    _symmetric = True
+
+
+# ------------------------------------------------------------------ GradCache over the in-batch-negatives losses
+def mini_batch_bounds(batch_size: int, mini_batch_size: int) -> List[tuple]:
+    """[(lo, hi)] of the mini-batches of a batch, in order; the last one may be ragged, and a mini_batch_size of at least
+    the batch gives one."""
+    if mini_batch_size < 1:
+        raise ValueError(f"mini_batch_size must be at least 1, {mini_batch_size} given")
+    return [(lo, min(batch_size, lo + mini_batch_size)) for lo in range(0, batch_size, mini_batch_size)]
+
+
+def slice_features(cols: List[Dict[str, torch.Tensor]], lo: int, hi: int) -> List[Dict[str, torch.Tensor]]:
+    """Rows lo .. hi-1 of every text column of an already-collated batch (views; whatever is not a tensor passes through)."""
+    return [{k: (v[lo:hi] if isinstance(v, torch.Tensor) else v) for k, v in col.items()} for col in cols]
+
+
+def _sentence_transformer_of(model):
+    """The SentenceTransformer behind `model`: the model itself, or what a wrapper holds as `.model`."""
+    while not hasattr(model, "_enc") and hasattr(model, "model"):
+        model = model.model
+    if not hasattr(model, "_enc"):
+        raise TypeError(f"{type(model).__name__} is not a SentenceTransformer of this package and wraps none as .model")
+    return model
+
+
+class _GradCacheFn(torch.autograd.Function):
+    """The loss value of step 2; its backward is step 3, the replay of the mini-batches with the cached gradients."""
+
+    @staticmethod
+    def forward(ctx, hook, loss, replay):
+        ctx.replay = replay
+        return loss.reshape(()).clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        ctx.replay(grad_output)
+        ctx.replay = None
+        return None, None, None
+
+
+class CachedMultipleNegativesRankingLoss(MultipleNegativesRankingLoss):
+    """MultipleNegativesRankingLoss at a batch size the activations of one pass would not fit (GradCache, Gao et al. 2021):
+      1. the batch is embedded in mini-batches of `mini_batch_size` examples without autograd;
+      2. loss and its gradient with respect to all embeddings come from ONE qst_mnrl_stream_loss call
+         (csrc/mnrl_stream.hip: no B x N score matrix either);
+      3. backward() runs every mini-batch again with autograd and pushes its slice of that gradient through the encoder.
+    Memory is that of one mini-batch whatever the batch; the price is one more forward. The second pass sees the masks of
+    the first: dropout masks here are a function of (seed, step, tensor, element), so the replay puts the encoder's step
+    counter back (HipEncoder.set_dropout_step) instead of saving and restoring generator states, and afterwards the counter
+    stands where step 1 left it. Both passes run at fit()'s `precision`. A foreign `similarity_fct` is scored by torch ops on
+    the full matrix, as in MultipleNegativesRankingLoss. Without autograd (torch.no_grad(), eval()) forward is steps 1 and 2
+    without gradients. Not supported yet: a data-parallel fit() (refused there), and MatryoshkaLoss around it."""
+    _replays_mini_batches = True        # what fit() refuses in a data-parallel world
+
+    def __init__(self, model, scale: float = 20.0, similarity_fct=util.cos_sim, mini_batch_size: int = 32,
+                 show_progress_bar: bool = False, fused: bool = True):
+        super().__init__(model, scale, similarity_fct, fused)
+        if mini_batch_size < 1:
+            raise ValueError(f"mini_batch_size must be at least 1, {mini_batch_size} given")
+        self.mini_batch_size = int(mini_batch_size)
+        self.show_progress_bar = show_progress_bar
+
+    def _scores_in_torch(self, a, c):
+        scores = self.similarity_fct(a, c) * self.scale
+        target = torch.arange(scores.shape[0], device=scores.device)
+        loss = torch.nn.functional.cross_entropy(scores, target)
+        if self._symmetric:
+            loss = (loss + torch.nn.functional.cross_entropy(scores[:, :scores.shape[0]].t(), target)) / 2
+        return loss
+
+    def _loss_and_cache(self, a, c, want_grads: bool):
+        """Step 2: the loss [1] and, with want_grads, d loss / d a and d loss / d c."""
+        sim = self._kernel_sim()
+        if sim is not None:
+            return mnrl_stream_loss_raw(a, c, sim, self.scale, self._symmetric, want_grads=want_grads)
+        if not want_grads:
+            return self._scores_in_torch(a, c).reshape(1), [None, None]
+        with torch.enable_grad():
+            a, c = a.requires_grad_(True), c.requires_grad_(True)
+            loss = self._scores_in_torch(a, c)
+            grads = torch.autograd.grad(loss, [a, c])
+        return loss.detach().reshape(1), [g.to(torch.float32) for g in grads]
+
+    def _mini_batches(self, bounds):
+        if not self.show_progress_bar:
+            return bounds
+        from tqdm.autonotebook import tqdm
+        return tqdm(bounds, desc="Mini-batches", leave=False)
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor = None) -> torch.Tensor:
+        cols = list(sentence_features)
+        k = len(cols)
+        if k < 2:
+            raise ValueError(f"{type(self).__name__} takes 2 or more text columns per example, {k} given")
+        st = _sentence_transformer_of(self.model)
+        enc = st._enc
+        B = cols[0]["input_ids"].shape[0]
+        bounds = mini_batch_bounds(B, self.mini_batch_size)
+        want_grads = torch.is_grad_enabled() and st.training
+
+        # 1. every mini-batch without autograd, at the precision (and with the masks) its replay will have
+        steps, parts = [], []
+        with torch.no_grad(), st.no_grad_passes_at_training_precision():
+            for lo, hi in self._mini_batches(bounds):
+                steps.append(enc.dropout_step)
+                parts.append([r.to(torch.float32) for r in self._embed(slice_features(cols, lo, hi), k)])
+        end = enc.dropout_step
+        reps = [torch.cat([p[j] for p in parts], 0) if len(parts) > 1 else parts[0][j] for j in range(k)]
+        a = reps[0].contiguous()
+        c = (reps[1] if k == 2 else torch.cat(reps[1:], 0)).contiguous()
+        del parts, reps
+
+        # 2. the loss and the gradient cache
+        loss, (grad_a, grad_c) = self._loss_and_cache(a, c, want_grads)
+        if not want_grads:
+            return loss.reshape(())
+
+        # 3. backward(): one mini-batch's activation arena at a time
+        def replay(grad_output):
+            g = _upstream(grad_output)                  # a device scalar: under use_amp it carries the loss scale
+            with torch.enable_grad():
+                for (lo, hi), step in zip(self._mini_batches(bounds), steps):
+                    enc.set_dropout_step(step)
+                    again = self._embed(slice_features(cols, lo, hi), k)
+                    cached = [grad_a[lo:hi]] + [grad_c[(j - 1) * B + lo:(j - 1) * B + hi] for j in range(1, k)]
+                    torch.autograd.backward(again, [(d * g).to(r.dtype) for d, r in zip(cached, again)])
+            enc.set_dropout_step(end)
+
+        hook = torch.zeros((), device=a.device, requires_grad=True)
+        return _GradCacheFn.apply(hook, loss, replay)
+
+
+class CachedMultipleNegativesSymmetricRankingLoss(CachedMultipleNegativesRankingLoss):
+    """MultipleNegativesSymmetricRankingLoss by the three steps of CachedMultipleNegativesRankingLoss."""
     _symmetric = True
 
 
@@ -1247,6 +1444,9 @@ class MatryoshkaLoss(nn.Module):
             raise ValueError("MatryoshkaLoss cannot wrap SoftmaxLoss: its classifier has a fixed input width")
         if isinstance(loss, MSELoss):
             raise ValueError("MatryoshkaLoss cannot wrap MSELoss: the teacher's vectors have the full width")
+        if isinstance(loss, CachedMultipleNegativesRankingLoss):
+            raise ValueError(f"MatryoshkaLoss cannot wrap {type(loss).__name__} yet: the cached losses embed in mini-batches "
+                             f"and replay them in backward(), and the per-width losses are not part of that replay")
         dims = [int(d) for d in matryoshka_dims]
         if not dims:
             raise ValueError("matryoshka_dims is empty")
