@@ -344,6 +344,41 @@ int qst_mnrl_stream_loss(const float* a, const float* c, int B, int N, int D, in
                          void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * GISTEmbedLoss and CachedGISTEmbedLoss of sentence-transformers 2.3 / 3.x (version 119; csrc/gist.hip): in-batch negatives
+ * that a frozen guide model filters. x fp32 [K * B, D]: the student's K >= 2 text columns stacked in column order (anchors a,
+ * positives p, hard negatives n_1 ...); g fp32 [K * B, Dg]: the guide's embeddings of the same texts, Dg independent of D;
+ * rows contiguous. With a hat = F.normalize(p=2, dim=1, eps=1e-12), row i has (K + 1) * B logits
+ *   ap[i, j] = a_hat_i . p_hat_j, aa[i, j] = a_hat_i . a_hat_j, pp[i, j] = p_hat_i . p_hat_j, an_k[i, j] = a_hat_i . n_hat_k,j,
+ * each divided by temperature; the guide has the same blocks from g, undivided, and thr_i = its ap[i, i]. An entry is removed
+ * (probability and gradient exactly 0) when guide entry > bound_i, a strict comparison:
+ *   QST_GIST_ABSOLUTE bound_i = thr_i - margin        QST_GIST_RELATIVE bound_i = thr_i * (1 - margin)
+ * (margin = 0 is bound_i = thr_i under both: the original rule). The target ap[i, i] is kept by index, whatever the margin and
+ * whatever the guide's value there; a NaN guide entry compares false and stays.
+ *   out_loss[0] = mean_i(logsumexp(row i) - ap[i, i] / temperature)
+ * grad_x [K * B, D] or NULL = forward only (nothing but out_loss is written): the gradient with respect to every student
+ * column, through both sides of aa and pp and through the normalisation (a row with |x| < 1e-12 as in qst_mnrl_loss); the guide
+ * gets none. grad_out: fp32 [1] on the DEVICE (NULL = 1), it multiplies the finished gradients.
+ * Anchors and positives are walked in strips of strip_rows rows: 0 = the library's choice (the largest multiple of 64 whose
+ * two fp32 strips strip_rows x ldS, ldS = (K + 1) * B rounded up to 4 -- student logits and guide scores -- fit 64 MiB together,
+ * at least 64, at most B rounded up to 64), otherwise a positive multiple of 64. No B x B tensor exists outside the strips:
+ * beyond them the workspace holds four arrays of K * B floats, one of B, and the partial sums of a strip's row-side products
+ * (ceil(K * B / 4096) x strip_rows x D floats when K * B > 4096) -- linear in B at fixed K, D, Dg and strip_rows.
+ * Contract as qst_mnrl_stream_loss: B < 1, K < 2, D < 1, Dg < 1, a NULL x, g, out_loss or workspace, a temperature that is not
+ * finite and positive, a margin that is not finite, another margin_strategy, a strip_rows that is neither 0 nor a positive
+ * multiple of 64 (workspace size 0 too), a workspace smaller than qst_gist_workspace_bytes or not 4-byte aligned:
+ * QST_ERR_BAD_ARG before any launch, nothing written. (K + 1) * B, strip_rows x ldS, K * B * D or K * B * Dg past 2^31 - 1:
+ * QST_ERR_UNSUPPORTED. All products run on the fp32 matrix cores (csrc/fp32_mgemm.h, shared with mnrl_stream.hip). No
+ * atomics, no host synchronisation, capturable in a HIP graph, bit-identical from call to call. 3 + 5 s launches forward and
+ * 4 + 9 s with gradients over s strips (one more per strip and row-side product whose K is chunked). out_loss is bit-identical
+ * for every strip_rows; the gradients, summed over the strips, may differ between strip_rows by rounding.
+ */
+enum { QST_GIST_ABSOLUTE = 0, QST_GIST_RELATIVE = 1 };
+size_t qst_gist_workspace_bytes(int B, int K, int D, int Dg, int strip_rows);
+int qst_gist_loss(const float* x, const float* g, int B, int K, int D, int Dg, float temperature, int margin_strategy,
+                  float margin, int strip_rows, float* out_loss, const float* grad_out, float* grad_x,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * MatryoshkaLoss over (Symmetric)MultipleNegativesRankingLoss (version 116; csrc/mnrl_nested.hip): the loss above at K nested
  * prefixes of the embedding in one call. a, c, B, N, D, scale, symmetric as for qst_mnrl_loss. dims and weights are HOST
  * arrays of K entries: K distinct widths 1 <= d_k <= D in any order, 1 <= K <= 8, and finite weights. For each k

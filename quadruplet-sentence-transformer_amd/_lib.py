@@ -104,6 +104,9 @@ SIGNATURES = {
     "qst_mnrl_stream_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "qst_mnrl_stream_loss": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp,
                                        vp, C.c_size_t, vp]),
+    "qst_gist_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "qst_gist_loss": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, vp, vp, vp,
+                                vp, C.c_size_t, vp]),
     "qst_mnrl_nested_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "qst_mnrl_nested_loss": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, c_i32p, c_f32p, C.c_int, C.c_float, C.c_int, vp, vp,
                                        vp, vp, vp, vp, C.c_size_t, vp]),

@@ -29,6 +29,12 @@ ranks. `data.NoDuplicatesDataLoader` is the loader these losses are meant to be 
 autograd, loss and embedding gradients come from one qst_mnrl_stream_loss call (csrc/mnrl_stream.hip: strips of anchors, no
 B x N score matrix), and backward() replays the mini-batches with autograd under the same dropout masks. Single process only.
 
+`GISTEmbedLoss` and `CachedGISTEmbedLoss` (sentence-transformers 2.3 / 3.x) are in-batch negatives filtered by a frozen
+`guide` model: anchors against positives, anchors and hard negatives, positives against positives, and whatever the guide
+scores above the anchor's own positive leaves the softmax. Both score matrices, the mask, the loss and the gradients of
+every column are one qst_gist_loss call (csrc/gist.hip, strips as in mnrl_stream.hip); the cached form follows the three
+GradCache steps with the guide embedded per mini-batch and not replayed.
+
 `BatchHardTripletLoss`, `BatchHardSoftMarginTripletLoss`, `BatchSemiHardTripletLoss` and `BatchAllTripletLoss` take ONE text
 column and an integer class label per example, and mine their triplets among the B x B distances of the batch at every
 step: distance matrix, mining, loss and the gradient through the selections are qst_batch_triplet_loss
@@ -80,6 +86,8 @@ _SIM_CODE = {"dot": SCORE_DOT, "cos": SCORE_COS, SCORE_DOT: SCORE_DOT, SCORE_COS
 BT_HARD, BT_HARD_SOFT, BT_SEMIHARD, BT_ALL = range(4)      # QST_BT_*: what qst_batch_triplet_loss takes as `kind`
 PAIRSIM_COS, PAIRSIM_ANGLE = 0, 1                 # QST_PAIRSIM_*: what qst_cosent_loss takes as `sim`
 _PAIRSIM_CODE = {"cos": PAIRSIM_COS, "angle": PAIRSIM_ANGLE, PAIRSIM_COS: PAIRSIM_COS, PAIRSIM_ANGLE: PAIRSIM_ANGLE}
+GIST_ABSOLUTE, GIST_RELATIVE = 0, 1               # QST_GIST_*: what qst_gist_loss takes as `margin_strategy`
+_GIST_CODE = {"absolute": GIST_ABSOLUTE, "relative": GIST_RELATIVE, GIST_ABSOLUTE: GIST_ABSOLUTE, GIST_RELATIVE: GIST_RELATIVE}
 
 
 # ------------------------------------------------------------------ direct calls (contiguous fp32 HIP tensors [B, D])
@@ -163,6 +171,25 @@ def mnrl_stream_loss_raw(a, c, sim, scale: float, symmetric: bool, strip_rows: i
                                             _lib.ptr(grads[0]), _lib.ptr(grads[1]), ws.data_ptr(), nbytes,
                                             _lib.current_stream_ptr()), "qst_mnrl_stream_loss")
     return out, grads
+
+
+def gist_loss_raw(x, g, K: int, temperature: float, margin_strategy, margin: float, strip_rows: int = 0,
+                  grad_out: Optional[torch.Tensor] = None, want_grads: bool = False):
+    """qst_gist_loss on contiguous fp32 HIP tensors x [K * B, D] (the student's K text columns stacked: anchors, positives,
+    hard negatives) and g [K * B, Dg] (the guide's embeddings of the same texts): the loss [1] and, with want_grads, grad_x
+    times grad_out (a device scalar; None = 1), else None. margin_strategy "absolute" / "relative" or GIST_*."""
+    lib = _lib.load()
+    (rows, D), Dg = x.shape, g.shape[1]
+    B = rows // K
+    out = torch.empty(1, dtype=torch.float32, device=x.device)
+    grad = torch.empty_like(x) if want_grads else None
+    nbytes = int(lib.qst_gist_workspace_bytes(B, K, D, Dg, int(strip_rows)))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.qst_gist_loss(x.data_ptr(), g.data_ptr(), B, K, D, Dg, float(temperature), _GIST_CODE[margin_strategy],
+                                     float(margin), int(strip_rows), out.data_ptr(), _lib.ptr(grad_out), _lib.ptr(grad),
+                                     ws.data_ptr(), nbytes, _lib.current_stream_ptr()), "qst_gist_loss")
+    return out, grad
 
 
 NESTED_MAX_DIMS = 8                                # the K qst_mnrl_nested_loss takes
@@ -351,6 +378,21 @@ class _MnrlStreamFn(torch.autograd.Function):
         return grads[0].to(ctx.in_dtypes[0]), grads[1].to(ctx.in_dtypes[1]), None, None, None, None
 
 
+class _GistFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, g, K, temperature, margin_strategy, margin, strip_rows):
+        xs = _f32((x, g))
+        out, _ = gist_loss_raw(xs[0], xs[1], K, temperature, margin_strategy, margin, strip_rows)
+        ctx.save_for_backward(*xs)
+        ctx.hp, ctx.in_dtype = (K, temperature, margin_strategy, margin, strip_rows), x.dtype
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        _, grad = gist_loss_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
+        return grad.to(ctx.in_dtype), None, None, None, None, None, None
+
+
 class _MnrlNestedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, c, dims, weights, scale, symmetric):
@@ -517,6 +559,41 @@ def multiple_negatives_ranking_loss_stream(a: torch.Tensor, c: torch.Tensor, sca
         raise ValueError(f"strip_rows is 0 or a positive multiple of 64, {strip_rows} given")
     _check_mnrl_args("multiple_negatives_ranking_loss_stream", a, c, scale, sim)
     return _MnrlStreamFn.apply(a, c, sim, float(scale), bool(symmetric), int(strip_rows))
+
+
+def _check_gist_hp(temperature: float, margin_strategy: str, margin: float) -> None:
+    if not (temperature > 0 and temperature < float("inf")):
+        raise ValueError(f"temperature must be positive and finite, {temperature} given")
+    if margin_strategy not in ("absolute", "relative"):
+        raise ValueError(f"margin_strategy is 'absolute' or 'relative', {margin_strategy!r} given")
+    if not (margin > float("-inf") and margin < float("inf")):
+        raise ValueError(f"margin must be finite, {margin} given")
+
+
+def gist_embed_loss(reps, guide_reps, temperature: float = 0.01, margin_strategy: str = "absolute", margin: float = 0.0,
+                    strip_rows: int = 0) -> torch.Tensor:
+    """GISTEmbedLoss on embeddings: `reps` the student's K >= 2 text columns [B, D] (anchors, positives, hard negatives ...),
+    `guide_reps` the guide's embeddings of the same texts [B, Dg]. Every anchor is scored against all positives, anchors and
+    hard negatives and every positive against all positives (cosine / temperature); a candidate the guide finds more similar
+    than the anchor's own positive -- guide score > thr_i - margin ("absolute") or thr_i * (1 - margin) ("relative") --
+    leaves the softmax, the positive itself never does. One qst_gist_loss call, differentiable in `reps`; the guide gets no
+    gradient. strip_rows as in multiple_negatives_ranking_loss_stream."""
+    reps, guide_reps = list(reps), list(guide_reps)
+    if len(reps) < 2 or len(guide_reps) != len(reps):
+        raise ValueError(f"gist_embed_loss takes 2 or more text columns and as many guide columns, {len(reps)} and "
+                         f"{len(guide_reps)} given")
+    _check_gist_hp(temperature, margin_strategy, margin)
+    if strip_rows < 0 or strip_rows % 64 != 0:
+        raise ValueError(f"strip_rows is 0 or a positive multiple of 64, {strip_rows} given")
+    for what, xs in (("student", reps), ("guide", guide_reps)):
+        if any(x.dim() != 2 or x.shape != xs[0].shape for x in xs) or xs[0].shape[0] < 1 or xs[0].shape[1] < 1:
+            raise ValueError(f"gist_embed_loss: the {what} columns must all have the same shape (B, D), B and D at least 1")
+    if guide_reps[0].shape[0] != reps[0].shape[0]:
+        raise ValueError(f"gist_embed_loss: {reps[0].shape[0]} student rows but {guide_reps[0].shape[0]} guide rows")
+    if not all(x.is_cuda for x in reps + guide_reps):
+        raise _lib.QstError("gist_embed_loss runs on the HIP device only (inputs are CPU tensors; no CPU path)")
+    return _GistFn.apply(torch.cat(reps, 0), torch.cat([r.detach() for r in guide_reps], 0), len(reps), float(temperature),
+                         margin_strategy, float(margin), int(strip_rows))
 
 
 def matryoshka_mnrl_loss(a: torch.Tensor, c: torch.Tensor, dims, weights=None, scale: float = 20.0,
@@ -975,6 +1052,149 @@ class CachedMultipleNegativesRankingLoss(MultipleNegativesRankingLoss):
 class CachedMultipleNegativesSymmetricRankingLoss(CachedMultipleNegativesRankingLoss):
     """MultipleNegativesSymmetricRankingLoss by the three steps of CachedMultipleNegativesRankingLoss."""
     _symmetric = True
+
+
+# ------------------------------------------------------------------ guided in-batch negatives
+def _synthetic_ids_agree(a, b) -> bool:
+    """Two models without vocabulary files hash a text to the same ids when their stand-in tokenizers agree."""
+    ta, tb = a._synthetic_tokenizer, b._synthetic_tokenizer
+    return (a.cfg.vocab_size, ta.cls_id, ta.sep_id, ta.pad_id) == (b.cfg.vocab_size, tb.cls_id, tb.sep_id, tb.pad_id)
+
+
+def _must_retokenize(st, guide) -> bool:
+    """sentence-transformers' rule: the guide reads the model's token ids unless its vocabulary or max_seq_length differs;
+    then the ids are decoded and tokenised again by the guide. Ids of a stand-in tokenizer (a model without vocabulary files)
+    cannot be decoded, and a guide with one cannot tokenise real text the same way: such a pair raises instead of scoring
+    garbage."""
+    if st.tokenizer is None and guide.tokenizer is None:
+        if _synthetic_ids_agree(st, guide) and st.max_seq_length == guide.max_seq_length:
+            return False
+        raise ValueError("GISTEmbedLoss: model and guide have no vocabulary files and their stand-in tokenizers or "
+                         "max_seq_length differ; the model's token ids cannot be decoded for the guide")
+    if st.tokenizer is None or guide.tokenizer is None:
+        raise ValueError("GISTEmbedLoss: one of model and guide has a real vocabulary and the other a stand-in tokenizer; "
+                         "the model's token ids cannot be turned into the guide's")
+    return st.tokenizer.get_vocab() != guide.tokenizer.get_vocab() or st.max_seq_length != guide.max_seq_length
+
+
+class GISTEmbedLoss(_TupleLoss):
+    """sentence-transformers' GISTEmbedLoss (Solatorio 2024): MultipleNegativesRankingLoss whose in-batch negatives a frozen
+    `guide` model filters. Each example is (anchor, positive[, hard negatives ...]); anchor i is scored against every positive,
+    every anchor and every hard negative of the batch, and positive i against every positive (cosine / temperature). A
+    candidate the guide finds more similar to the anchor than the anchor's own positive is a probable false negative and
+    leaves the softmax: guide score > thr_i - margin (`margin_strategy="absolute"`) or > thr_i * (1 - margin) ("relative"),
+    thr_i the guide's score of (anchor i, positive i); margin 0 is the paper's rule. A text that appears twice in a batch is
+    removed that way too. Student scores, guide scores, mask, loss and the gradients of all columns are ONE qst_gist_loss call
+    (csrc/gist.hip).
+
+    `guide` is a SentenceTransformer of this package, of any width. It is embedded under torch.no_grad() in eval mode and is
+    not a submodule of the loss: train() does not reach it, and fit() neither steps nor checkpoints it. If its vocabulary or
+    max_seq_length differs from the model's, the model's input_ids are decoded and tokenised again for it. `labels` is not
+    looked at (see MultipleNegativesRankingLoss for fit() and empty labels)."""
+    reduction = "mean"
+
+    def __init__(self, model, guide, temperature: float = 0.01, margin_strategy: str = "absolute", margin: float = 0.0,
+                 fused: bool = True):
+        super().__init__(model, fused)
+        _check_gist_hp(temperature, margin_strategy, margin)
+        from .sentence_transformer import SentenceTransformer
+        if not isinstance(guide, SentenceTransformer):
+            raise TypeError(f"guide must be a SentenceTransformer of this package, {type(guide).__name__} given")
+        object.__setattr__(self, "guide", guide.eval())     # not registered: a frozen model, outside train() and parameters()
+        self.temperature = temperature
+        self.margin_strategy = margin_strategy
+        self.margin = margin
+        self.must_retokenize = _must_retokenize(_sentence_transformer_of(model), guide)
+
+    def get_config_dict(self):
+        return {"guide": getattr(self.guide, "_model_card_name", None) or type(self.guide).__name__,
+                "temperature": self.temperature, "margin_strategy": self.margin_strategy, "margin": self.margin}
+
+    def _guide_columns(self, cols):
+        if not self.must_retokenize:
+            return [dict(c) for c in cols]
+        tok = _sentence_transformer_of(self.model).tokenizer
+        dev = self.guide.device
+        return [{k: v.to(dev) for k, v in self.guide.tokenize(tok.batch_decode(c["input_ids"], skip_special_tokens=True)).items()}
+                for c in cols]
+
+    def _embed_guide(self, cols) -> torch.Tensor:
+        """The guide's embeddings of every column, stacked [K * B, Dg] fp32: no autograd, eval mode (no dropout)."""
+        guide = self.guide
+        with torch.no_grad():
+            guide.eval()
+            reps = encode_columns_fused(guide, self._guide_columns(cols))
+        return torch.cat([r.to(torch.float32) for r in reps], 0)
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor = None) -> torch.Tensor:
+        cols = list(sentence_features)
+        if len(cols) < 2:
+            raise ValueError(f"{type(self).__name__} takes 2 or more text columns per example, {len(cols)} given")
+        guide_reps = self._embed_guide(cols)
+        reps = self._embed(cols, len(cols))
+        return gist_embed_loss(reps, guide_reps.chunk(len(cols), 0), self.temperature, self.margin_strategy, self.margin)
+
+
+class CachedGISTEmbedLoss(GISTEmbedLoss):
+    """GISTEmbedLoss by the three steps of CachedMultipleNegativesRankingLoss (GradCache): (1) every mini-batch of
+    `mini_batch_size` examples is embedded without autograd, by the model and by the guide; (2) the loss and its gradient with
+    respect to all student embeddings come from ONE qst_gist_loss call, which holds no B x B tensor; (3) backward() replays the
+    model's mini-batches with autograd under the masks of the first pass. The guide is not replayed. Single process only."""
+    _replays_mini_batches = True        # what fit() refuses in a data-parallel world
+
+    def __init__(self, model, guide, temperature: float = 0.01, mini_batch_size: int = 32, show_progress_bar: bool = False,
+                 margin_strategy: str = "absolute", margin: float = 0.0):
+        super().__init__(model, guide, temperature, margin_strategy, margin)
+        if mini_batch_size < 1:
+            raise ValueError(f"mini_batch_size must be at least 1, {mini_batch_size} given")
+        self.mini_batch_size = int(mini_batch_size)
+        self.show_progress_bar = show_progress_bar
+
+    _mini_batches = CachedMultipleNegativesRankingLoss._mini_batches
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor = None) -> torch.Tensor:
+        cols = list(sentence_features)
+        k = len(cols)
+        if k < 2:
+            raise ValueError(f"{type(self).__name__} takes 2 or more text columns per example, {k} given")
+        st = _sentence_transformer_of(self.model)
+        enc = st._enc
+        B = cols[0]["input_ids"].shape[0]
+        bounds = mini_batch_bounds(B, self.mini_batch_size)
+        want_grads = torch.is_grad_enabled() and st.training
+
+        # 1. every mini-batch without autograd: the guide's embeddings, and the student's at the precision (and with the
+        #    masks) its replay will have
+        steps, parts, guide_parts = [], [], []
+        with torch.no_grad(), st.no_grad_passes_at_training_precision():
+            for lo, hi in self._mini_batches(bounds):
+                mini = slice_features(cols, lo, hi)
+                guide_parts.append(self._embed_guide(mini).view(k, hi - lo, -1))
+                steps.append(enc.dropout_step)
+                parts.append(torch.stack([r.to(torch.float32) for r in self._embed(mini, k)], 0))
+        end = enc.dropout_step
+        x = torch.cat(parts, 1).reshape(k * B, -1)      # [k, B, D] stacked in column order
+        g = torch.cat(guide_parts, 1).reshape(k * B, -1)
+        del parts, guide_parts
+
+        # 2. the loss and the gradient cache
+        loss, grad_x = gist_loss_raw(x, g, k, self.temperature, self.margin_strategy, self.margin, want_grads=want_grads)
+        if not want_grads:
+            return loss.reshape(())
+
+        # 3. backward(): one mini-batch's activation arena at a time, the student only
+        def replay(grad_output):
+            scale = _upstream(grad_output)              # a device scalar: under use_amp it carries the loss scale
+            with torch.enable_grad():
+                for (lo, hi), step in zip(self._mini_batches(bounds), steps):
+                    enc.set_dropout_step(step)
+                    again = self._embed(slice_features(cols, lo, hi), k)
+                    cached = [grad_x[j * B + lo:j * B + hi] for j in range(k)]
+                    torch.autograd.backward(again, [(d * scale).to(r.dtype) for d, r in zip(cached, again)])
+            enc.set_dropout_step(end)
+
+        hook = torch.zeros((), device=x.device, requires_grad=True)
+        return _GradCacheFn.apply(hook, loss, replay)
 
 
 # ------------------------------------------------------------------ the batch-mining triplet losses
@@ -1444,7 +1664,7 @@ class MatryoshkaLoss(nn.Module):
             raise ValueError("MatryoshkaLoss cannot wrap SoftmaxLoss: its classifier has a fixed input width")
         if isinstance(loss, MSELoss):
             raise ValueError("MatryoshkaLoss cannot wrap MSELoss: the teacher's vectors have the full width")
-        if isinstance(loss, CachedMultipleNegativesRankingLoss):
+        if getattr(loss, "_replays_mini_batches", False):       # the cached in-batch-negatives losses, GIST's included
             raise ValueError(f"MatryoshkaLoss cannot wrap {type(loss).__name__} yet: the cached losses embed in mini-batches "
                              f"and replay them in backward(), and the per-width losses are not part of that replay")
         dims = [int(d) for d in matryoshka_dims]
