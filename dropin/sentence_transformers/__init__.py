@@ -12,6 +12,6 @@ from quadruplet_sentence_transformer_amd.sentence_transformer import InputExampl
 # sentence_transformers.CrossEncoder (models/evaluators.py:31): the HIP cross-encoder; a name with no checkpoint on disk
 # still constructs, and predict() raises
 from quadruplet_sentence_transformer_amd.cross_encoder import CrossEncoder  # noqa: E402,F401
-from . import util, evaluation, models, cross_encoder, losses, datasets  # noqa: E402,F401
+from . import util, evaluation, models, cross_encoder, losses, datasets, quantization  # noqa: E402,F401
 
 __version__ = "2.2.2+qst_amd"

@@ -412,6 +412,56 @@ int qst_topk_stream(const float* queries, const float* corpus, int nq, int nc, i
                     int64_t query_base, int64_t corpus_base, int exclude_self, float max_score,
                     float* run_scores, int64_t* run_index, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Embedding quantization and search on the codes (version 120; csrc/quantize.hip; sentence_transformers.quantization of 2.6+). All of
+ * it launches on `stream` with no host synchronisation and no atomics, the workspace is the caller's, and every argument
+ * is checked before the first launch: a NULL pointer, a non-positive size, another kind or a pointer below its alignment is
+ * QST_ERR_BAD_ARG, a size the kernels are not built for QST_ERR_UNSUPPORTED, a short workspace QST_ERR_WORKSPACE. */
+enum { QST_QUANT_INT8 = 0, QST_QUANT_UINT8 = 1, QST_QUANT_BINARY = 2, QST_QUANT_UBINARY = 3 };
+
+/* out f32 [2, dim]: row 0 the minimum, row 1 the maximum of every column of x f32 [n, dim] (upstream's `ranges`). A NaN
+ * anywhere in a column makes both of its outputs NaN (np.min / np.max). Two stages of a fixed shape: 128 row slices, then
+ * one thread per column over the 128 partial results -- the same sums of comparisons for every n. */
+size_t qst_column_ranges_workspace_bytes(int64_t n, int dim);
+int qst_column_ranges(const float* x, int64_t n, int dim, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* x f32 [n, dim] (4-byte aligned) to codes:
+ *   QST_QUANT_UBINARY  out u8 [n, ceil(dim / 8)] = np.packbits(x > 0, axis=-1): bit 7 - (j % 8) of byte j / 8; NaN, 0.0 and
+ *                      -0.0 give 0, a positive denormal 1, the pad bits of the last byte are 0.
+ *   QST_QUANT_BINARY   the same byte - 128 as int8 (= the byte xor 0x80).
+ *   QST_QUANT_UINT8    ranges f32 [2, dim] required (lo = row 0, hi = row 1); in fp32, every operation correctly rounded:
+ *                      t = (x - lo) / ((hi - lo) / 255.0f), code = trunc(t) saturated to [0, 255].
+ *   QST_QUANT_INT8     code = trunc(t - 128.0f) saturated to [-128, 127], out i8 [n, dim].
+ *                      A NaN t, or hi == lo, gives the lowest code (0 / -128).
+ * ranges is ignored for the two bit kinds. 16-byte reads where dim % 4 == 0 and the bases are 16-byte aligned. */
+int qst_quantize_rows(const float* x, int64_t n, int dim, int kind, const float* ranges, void* out, void* stream);
+
+/* qst_topk_stream on packed bits: the score of a pair is -(number of differing bits) as f32, so larger is better; global
+ * ids, exclude_self, -inf / -1 padding, k <= 1024, query blocks of 2,048 and the order (score descending, id ascending,
+ * through qst_topk_merge_rows) are qst_topk_stream's. QST_QUANT_BINARY and QST_QUANT_UBINARY codes give the same distances
+ * (the xor cancels 0x80), so the entry takes raw bytes. nbytes % 4 == 0, else QST_ERR_UNSUPPORTED; both bases 4-byte
+ * aligned; 16-byte loads only where nbytes % 16 == 0 and both bases are 16-byte aligned. The workspace is one
+ * [min(nq, 2048), chunk rounded up to 4] f32 score block. */
+size_t qst_topk_hamming_workspace_bytes(int nq, int chunk, int nbytes);
+int qst_topk_hamming_stream(const uint8_t* queries, const uint8_t* corpus, int nq, int nc, int nbytes, int k, int chunk,
+                            int64_t query_base, int64_t corpus_base, int exclude_self, float* run_scores,
+                            int64_t* run_index, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same on int8 codes [*, dim]: the score is the exact int32 dot product (v_mfma_i32_32x32x32_i8) converted to f32.
+ * dim % 32 == 0 and dim <= 1024, else QST_ERR_UNSUPPORTED: then |score| <= 128 * 128 * 1024 = 2^24 and the f32 value, hence
+ * the ranking, is exact. Both bases 16-byte aligned. */
+size_t qst_topk_int8_workspace_bytes(int nq, int chunk, int dim);
+int qst_topk_int8_stream(const int8_t* queries, const int8_t* corpus, int nq, int nc, int dim, int k, int chunk,
+                         int64_t query_base, int64_t corpus_base, int exclude_self, float* run_scores, int64_t* run_index,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[r][p] = sum_j queries[r][j] * v(corpus[cand[r][p]][j]) for p < kc, accumulated in fp32; queries f32 [nq, dim], cand
+ * int64 / out f32 [nq, ld], ld >= kc. corpus holds nc rows of `kind` codes of width dim (bits: ceil(dim / 8) bytes a row).
+ * v is the bit (0 or 1; QST_QUANT_BINARY after undoing the 0x80) or the stored integer: upstream's rescoring products.
+ * cand < 0 gives -inf. The ids live on the device, so cand >= nc cannot be refused here: it is the caller's error; such a
+ * pair reads nothing and stores NaN. Columns kc .. ld of out are not written. */
+int qst_rescore_quantized(const float* queries, const void* corpus, int kind, int64_t nc, int dim, const int64_t* cand,
+                          int64_t ld, int nq, int kc, float* out, void* stream);
+
 /* Community detection (sentence-transformers 2.2.2 util.community_detection) without the n x n matrix. With S the cosine
  * scores of the rows of emb f32 [n, dim] among themselves -- prepared and multiplied exactly as qst_score_matrix and
  * qst_topk_stream do it (rows normalised with eps 1e-12, the split-bf16 x3 GEMM) -- and N(i) = { j : S[i, j] >= threshold }

@@ -233,6 +233,16 @@ SIGNATURES = {
     "qst_topk_stream_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "qst_topk_stream": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                   C.c_int, C.c_float, vp, vp, vp, C.c_size_t, vp]),
+    "qst_column_ranges_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "qst_column_ranges": (C.c_int, [vp, C.c_int64, C.c_int, vp, vp, C.c_size_t, vp]),
+    "qst_quantize_rows": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp]),
+    "qst_topk_hamming_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "qst_topk_hamming_stream": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                          vp, vp, vp, C.c_size_t, vp]),
+    "qst_topk_int8_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "qst_topk_int8_stream": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                       vp, vp, vp, C.c_size_t, vp]),
+    "qst_rescore_quantized": (C.c_int, [vp, vp, C.c_int, C.c_int64, C.c_int, vp, C.c_int64, C.c_int, C.c_int, vp, vp]),
     "qst_community_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "qst_community_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "qst_community_members": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,

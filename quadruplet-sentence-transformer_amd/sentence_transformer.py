@@ -400,13 +400,23 @@ class SentenceTransformer(nn.Module):
                output_value: str = "sentence_embedding", convert_to_numpy: bool = True,
                convert_to_tensor: bool = False, device: Optional[str] = None, normalize_embeddings: bool = False,
                precision: Optional[str] = None, truncate_dim: Optional[int] = None):
-        """precision: None = self.inference_precision; "bf16x3" = embeddings within rtol 1e-3/atol 1e-4 of fp32.
+        """precision: None = self.inference_precision; "bf16x3" = embeddings within rtol 1e-3/atol 1e-4 of fp32. One of
+        sentence-transformers' output names ("float32", "int8", "uint8", "binary", "ubinary") instead keeps the forward at
+        self.inference_precision and quantizes the whole result once (quantization.quantize_embeddings, after truncation
+        and normalisation; int8 / uint8 ranges over all sentences).
         truncate_dim: None = self.truncate_dim; the first `truncate_dim` columns of the sentence embedding are kept BEFORE
         normalize_embeddings is applied (sentence-transformers' order). token_embeddings are not truncated.
         output_value="token_embeddings": per sentence the final token states [n_tokens, H], trimmed to its attention mask's
         length, as ST 2.2.2 returns them (a list; tensors, or numpy arrays with convert_to_numpy)."""
         if output_value not in ("sentence_embedding", "token_embeddings"):
             raise NotImplementedError("output_value is 'sentence_embedding' or 'token_embeddings'")
+        # sentence-transformers' output precisions name the FORMAT of the result; the forward then runs at inference_precision
+        out_precision = precision if precision in ("float32", "int8", "uint8", "binary", "ubinary") else None
+        if out_precision is not None:
+            if output_value == "token_embeddings":
+                raise ValueError(f"precision={precision!r} quantizes sentence embeddings; it cannot be combined with "
+                                 "output_value='token_embeddings'")
+            precision = None
         if output_value == "token_embeddings":
             return self._encode_tokens(sentences, batch_size, convert_to_numpy and not convert_to_tensor, precision)
         cut = self.truncate_dim if truncate_dim is None else _checked_truncate_dim(truncate_dim)
@@ -432,7 +442,7 @@ class SentenceTransformer(nn.Module):
                     emb = emb.contiguous()
                     _lib.check(self._enc.lib.qst_normalize_rows(emb.data_ptr(), emb.shape[0], emb.shape[1], emb.data_ptr(),
                                                                 _lib.current_stream_ptr()), "qst_normalize_rows")
-                chunks.append(emb.cpu() if convert_to_numpy else emb)
+                chunks.append(emb.cpu() if convert_to_numpy and out_precision is None else emb)
         if chunks:
             allemb = torch.cat(chunks, 0)
         else:
@@ -440,6 +450,12 @@ class SentenceTransformer(nn.Module):
                 allemb = torch.zeros(0, self.get_sentence_embedding_dimension())
         inv = np.argsort(order)
         allemb = allemb[torch.as_tensor(inv, device=allemb.device)] if len(inv) else allemb
+        if out_precision is not None and len(inv):
+            # the whole result at once: int8 / uint8 take their ranges over all sentences, as upstream does
+            from .quantization import quantize_embeddings
+            allemb = quantize_embeddings(allemb.contiguous(), out_precision)
+            if convert_to_numpy:
+                allemb = allemb.cpu()
         if convert_to_numpy:
             allemb = allemb.numpy()
         if single:

@@ -354,6 +354,24 @@ def topk_stream(queries, corpus, k: int, mode="cos", chunk: int = STREAM_CHUNK, 
     return rs, ri
 
 
+def hamming_topk(queries, corpus, k: int, chunk: int = None, exclude_self: bool = False, state=None, query_base: int = 0,
+                 corpus_base: int = 0):
+    """topk_stream on packed sign bits ('binary' int8 or 'ubinary' uint8 codes of quantization.quantize_embeddings): the
+    score is -(Hamming distance). libqst qst_topk_hamming_stream; see quantization.hamming_topk."""
+    from . import quantization
+    return quantization.hamming_topk(queries, corpus, k, chunk=chunk, exclude_self=exclude_self, state=state,
+                                     query_base=query_base, corpus_base=corpus_base)
+
+
+def int8_topk(queries, corpus, k: int, chunk: int = None, exclude_self: bool = False, state=None, query_base: int = 0,
+              corpus_base: int = 0):
+    """topk_stream on int8 codes: the score is the exact integer dot product. libqst qst_topk_int8_stream; see
+    quantization.int8_topk."""
+    from . import quantization
+    return quantization.int8_topk(queries, corpus, k, chunk=chunk, exclude_self=exclude_self, state=state,
+                                  query_base=query_base, corpus_base=corpus_base)
+
+
 def _as_rows(x):
     """A tensor, a numpy array, a list of tensors or a single 1-D embedding -> a 2-D tensor (ST's accepted inputs)."""
     if isinstance(x, (list, tuple)):
