@@ -496,6 +496,38 @@ int qst_margin_mse_loss(const float* q, const float* p, const float* n, const fl
                         float* grad_q, float* grad_p, float* grad_n, float* scratch, void* stream);
 
 /*
+ * Distillation from a teacher's scores over a list of K candidates per query, candidate 0 the positive (version 121;
+ * csrc/listwise.hip): losses.DistillKLDivLoss (sentence-transformers 3.4) and losses.MarginMSELoss with several negatives
+ * (3.x). All tensors fp32. q [B, D]; docs [K, B, D] contiguous, candidate j of example b at (j * B + b) * D -- the text
+ * columns of one encoder pass stacked, as they come out of it. sim: QST_METRIC_DOT or QST_METRIC_COS_SIM, the latter with
+ * exactly qst_pair_metric's semantics (each norm clamped at 1e-8, a clamped norm passes no gradient), as qst_margin_mse_loss.
+ *   QST_LISTWISE_KL          labels [B, K], the teacher's scores. With s_j = sim(q, d_j) / T and t = softmax(labels / T)
+ *                            row_b = T^2 * sum_j t_j (log t_j - log_softmax(s)_j); a term with t_j == 0 is exactly 0 (torch's
+ *                            xlogy in nn.KLDivLoss). QST_REDUCE_MEAN divides by B (reduction="batchmean").
+ *                            d row / d sim_j = T (softmax(s)_j - t_j). Both softmaxes are taken around their maxima.
+ *   QST_LISTWISE_MARGIN_MSE  labels [B, K - 1], the teacher's margin per negative; K >= 2.
+ *                            row_b = sum_{j >= 1} (sim(q, d_0) - sim(q, d_j) - labels_{j-1})^2. QST_REDUCE_MEAN divides by
+ *                            B (K - 1) (nn.MSELoss() on [B, K - 1]). temperature is ignored.
+ * reduction QST_REDUCE_NONE / SUM / MEAN as qst_margin_mse_loss: out_loss [B] and grad_out [B] for NONE, [1] and [1]
+ * otherwise; grad_out lives on the DEVICE (NULL = ones) and multiplies the finished gradient. out_scores fp32 [B, K] or NULL
+ * receives the similarities (not divided by T). grad_q [B, D] and grad_docs [K, B, D] both NULL = forward only (nothing else
+ * is written); exactly one NULL is QST_ERR_BAD_ARG. Gradients are written, not accumulated. scratch fp32 [B] (may be NULL
+ * for QST_REDUCE_NONE).
+ * One wave per example: the query row stays in registers up to D = 2048, every candidate row is read once for its score and
+ * once more for the gradients (16-byte accesses when D % 4 == 0 and the pointers are 16-byte aligned, element by element
+ * otherwise; past D = 2048 the query streams too). Runs on the caller's stream without host synchronisation (capturable in
+ * a HIP graph). No atomics: the per-row values go through the one-workgroup second stage that sums them in double in a
+ * fixed order, so the same inputs give bit-identical outputs from call to call.
+ * B < 1, D < 1, a NULL q, docs, labels or out_loss, a NULL scratch where one is needed, another kind, sim or reduction, a
+ * temperature that is not finite and positive with QST_LISTWISE_KL, K == 1 with QST_LISTWISE_MARGIN_MSE: QST_ERR_BAD_ARG.
+ * K < 1 or K > 64 (lane j of the wave holds score j): QST_ERR_UNSUPPORTED. Both before any launch, nothing written.
+ */
+enum { QST_LISTWISE_KL = 0, QST_LISTWISE_MARGIN_MSE = 1 };
+int qst_listwise_distill_loss(const float* q, const float* docs, const float* labels, int B, int K, int D, int kind, int sim,
+                              float temperature, int reduction, float* out_loss, float* out_scores, const float* grad_out,
+                              float* grad_q, float* grad_docs, float* scratch, void* stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_grad_norm) + torch.optim.AdamW.step()
  * with ST fit()'s two parameter groups (/root/reference/training/main.py:128-148).
  *   n            : arena elements; decay is applied per segment as the layout says

@@ -117,6 +117,8 @@ SIGNATURES = {
     "qst_cosent_loss": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "qst_embed_mse": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "qst_margin_mse_loss": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "qst_listwise_distill_loss": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp,
+                                            vp, vp, vp, vp, vp]),
     "qst_clip_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                       C.c_float, C.c_float, C.c_int64, vp, vp, vp]),
     "qst_clip_adamw_step_joint": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float,

@@ -15,7 +15,7 @@
 static thread_local int g_last_hip_error = 0;
 extern "C" int qst_set_hip_error(int code) { g_last_hip_error = code; return code; }
 extern "C" int qst_last_hip_error(void) { return g_last_hip_error; }
-extern "C" int qst_version(void) { return 120; }
+extern "C" int qst_version(void) { return 121; }
 
 extern "C" const char* qst_strerror(int s) {
     switch (s) {

@@ -52,6 +52,12 @@ embedding of each example as its label ([B, D]: SentenceTransformer.smart_batchi
 difference, the squared error and all three gradients are one qst_margin_mse_loss call; any other callable
 `f(a, b) -> [B]` is called on the embeddings and the rest runs in torch.
 
+`DistillKLDivLoss` (sentence-transformers 3.4) and `MarginMSELoss` with four or more text columns (3.x) distil from the
+teacher's scores over a LIST per query -- (query, positive, negatives ...), K candidates, labels [B, K] scores or [B, K - 1]
+margins. The K similarities, the softmaxes and the divergence (or the K - 1 squared errors) and the gradients of all 1 + K
+columns are one qst_listwise_distill_loss call (csrc/listwise.hip) on the one buffer the fused encoder pass returns, for the
+same two similarity functions and up to 64 candidates; anything else is sentence-transformers' composition in torch ops.
+
 `SoftmaxLoss` is the one objective here with parameters of its own: an `nn.Linear` classifier on [u, v, |u - v|, u * v] whose
 weights live in a `loss_params.LossParameters`, a flat buffer the fused optimiser step takes next to the arena. Logits, cross
 entropy and all four gradients are csrc/softmax_head.hip (qst_softmax_head_fwd, qst_softmax_ce, qst_softmax_head_bwd).
@@ -291,6 +297,35 @@ def margin_mse_raw(q, p, n, labels, sim: int, reduction: int, grad_out: Optional
     return (out, grads, margin) if want_margin else (out, grads)
 
 
+LISTWISE_KL, LISTWISE_MARGIN_MSE = 0, 1           # QST_LISTWISE_*: what qst_listwise_distill_loss takes as `kind`
+_LISTWISE_CODE = {"kl": LISTWISE_KL, "margin_mse": LISTWISE_MARGIN_MSE, LISTWISE_KL: LISTWISE_KL,
+                  LISTWISE_MARGIN_MSE: LISTWISE_MARGIN_MSE}
+LISTWISE_MAX_K = 64                               # the candidates per query the kernel takes: lane j holds score j
+
+
+def listwise_distill_raw(q, docs, labels, kind, sim: int, temperature: float, reduction: int,
+                         grad_out: Optional[torch.Tensor] = None, want_grads: bool = False, want_scores: bool = False):
+    """qst_listwise_distill_loss on contiguous fp32 HIP tensors q [B, D], docs [K, B, D] (candidate 0 the positive) and
+    labels [B, K] (kind "kl" / LISTWISE_KL: the teacher's scores) or [B, K - 1] ("margin_mse": its margins): the loss per
+    row [B] or reduced [1], [grad_q, grad_docs] or [None, None], and with want_scores the similarities [B, K] as a third
+    result. sim METRIC_DOT or METRIC_COS_SIM."""
+    lib = _lib.load()
+    if not (q.is_cuda and docs.is_cuda and labels.is_cuda):
+        raise _lib.QstError("listwise_distill_raw runs on the HIP device only (inputs are CPU tensors; no CPU path)")
+    (B, D), K = q.shape, docs.shape[0]
+    out = torch.empty(B if reduction == 0 else 1, dtype=torch.float32, device=q.device)
+    scratch = torch.empty(B, dtype=torch.float32, device=q.device)
+    scores = torch.empty(B, K, dtype=torch.float32, device=q.device) if want_scores else None
+    grads = [torch.empty_like(q), torch.empty_like(docs)] if want_grads else [None, None]
+    with torch.cuda.device(q.device):
+        _lib.check(lib.qst_listwise_distill_loss(q.data_ptr(), docs.data_ptr(), labels.data_ptr(), B, K, D,
+                                                 _LISTWISE_CODE[kind], int(sim), float(temperature), int(reduction),
+                                                 out.data_ptr(), _lib.ptr(scores), _lib.ptr(grad_out), _lib.ptr(grads[0]),
+                                                 _lib.ptr(grads[1]), scratch.data_ptr(), _lib.current_stream_ptr()),
+                   "qst_listwise_distill_loss")
+    return (out, grads, scores) if want_scores else (out, grads)
+
+
 # ------------------------------------------------------------------ autograd (save the inputs, recompute in backward)
 def _f32(xs):
     return [x.detach().to(torch.float32).contiguous() for x in xs]
@@ -470,6 +505,22 @@ class _MarginMseFn(torch.autograd.Function):
     def backward(ctx, grad_output):
         _, grads = margin_mse_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
         return (*[g.to(dt) for g, dt in zip(grads, ctx.in_dtypes)], None, None, None)
+
+
+class _ListwiseDistillFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, docs, labels, kind, sim, temperature, red_code):
+        xs = _f32((q, docs))
+        y = labels.detach().to(torch.float32).contiguous()
+        out, _ = listwise_distill_raw(*xs, y, kind, sim, temperature, red_code)
+        ctx.save_for_backward(*xs, y)
+        ctx.hp, ctx.in_dtypes = (kind, sim, temperature, red_code), (q.dtype, docs.dtype)
+        return out if red_code == 0 else out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        _, grads = listwise_distill_raw(*ctx.saved_tensors, *ctx.hp, grad_out=_upstream(grad_output), want_grads=True)
+        return (*[g.to(dt) for g, dt in zip(grads, ctx.in_dtypes)], None, None, None, None, None)
 
 
 def _device_of(model) -> torch.device:
@@ -690,6 +741,44 @@ def margin_mse(q, p, n, labels, sim: int = METRIC_DOT, reduction: str = "mean") 
     _require_rows("margin_mse", q, p, n)
     _require_labels("margin_mse", labels, q.shape[0])
     return _MarginMseFn.apply(q, p, n, labels, int(sim), _RED_CODE[reduction])
+
+
+def _listwise_label_shape(kind: int, B: int, K: int) -> tuple:
+    return (B, K) if kind == LISTWISE_KL else (B, K - 1)
+
+
+def listwise_distill(q, docs, labels, kind="kl", sim: int = METRIC_DOT, temperature: float = 1.0,
+                     reduction: str = "mean") -> torch.Tensor:
+    """Distillation over a list of candidates per query: q [B, D], docs [K, B, D] (candidate 0 the positive, 1 <= K <= 64),
+    sim METRIC_DOT or METRIC_COS_SIM. kind "kl": temperature^2 * KL(softmax(labels / temperature) ||
+    softmax(sim(q, docs) / temperature)) per row, labels [B, K] the teacher's scores, "mean" over the batch (batchmean).
+    kind "margin_mse": sum over the negatives of (sim(q, docs_0) - sim(q, docs_j) - labels_{j-1})^2, labels [B, K - 1] the
+    teacher's margins, "mean" over all B (K - 1) of them. One qst_listwise_distill_loss call, differentiable in q and docs."""
+    if kind not in _LISTWISE_CODE:
+        raise ValueError(f"kind is 'kl' or 'margin_mse', {kind!r} given")
+    kind = _LISTWISE_CODE[kind]
+    if sim not in (METRIC_DOT, METRIC_COS_SIM):
+        raise ValueError(f"sim is METRIC_DOT or METRIC_COS_SIM, {sim!r} given")
+    if reduction not in _RED_CODE:
+        raise ValueError(f"reduction is 'none', 'sum' or 'mean', {reduction!r} given")
+    if q.dim() != 2 or docs.dim() != 3 or docs.shape[1:] != q.shape or q.shape[0] < 1 or q.shape[1] < 1:
+        raise ValueError(f"listwise_distill: queries (B, D) and candidates (K, B, D), {tuple(q.shape)} and "
+                         f"{tuple(docs.shape)} given")
+    (B, _), K = q.shape, docs.shape[0]
+    k_min = 2 if kind == LISTWISE_MARGIN_MSE else 1
+    if not k_min <= K <= LISTWISE_MAX_K:
+        raise ValueError(f"listwise_distill: {K} candidates per query; the kernel takes {k_min} to {LISTWISE_MAX_K}")
+    want = _listwise_label_shape(kind, B, K)
+    if tuple(labels.shape) != want:
+        raise ValueError(f"listwise_distill: the labels of {tuple(docs.shape)} candidates have the shape {want}; "
+                         f"{tuple(labels.shape)} given")
+    if kind == LISTWISE_KL and not (0.0 < float(temperature) < float("inf")):
+        raise ValueError(f"temperature must be finite and positive, {temperature!r} given")
+    if not (q.is_cuda and docs.is_cuda):
+        raise _lib.QstError("listwise_distill runs on the HIP device only (inputs are CPU tensors; no CPU path)")
+    if not labels.is_cuda:
+        raise _lib.QstError("listwise_distill runs on the HIP device only (labels are a CPU tensor; no CPU path)")
+    return _ListwiseDistillFn.apply(q, docs, labels, kind, int(sim), float(temperature), _RED_CODE[reduction])
 
 
 def quadruplet_eval_raw(a, p, q, n, want_dist: bool = False):
@@ -1344,11 +1433,35 @@ class MSELoss(_TupleLoss):
         return embed_mse(rep, labels)
 
 
+def _list_operands(reps: List[torch.Tensor]):
+    """(query [B, D], candidates [K, B, D]) of the embedded text columns, as qst_listwise_distill_loss takes them. The columns
+    of one fused pass are the row blocks of one [(1 + K) * B, D] buffer (encode_columns_fused splits it), and the candidates
+    are then a view of its rows from B on; columns embedded one by one are stacked."""
+    q, cands = reps[0], reps[1:]
+    B, D = q.shape
+    whole = getattr(q, "_base", None)
+    if (whole is not None and whole.dim() == 2 and tuple(whole.shape) == (len(reps) * B, D) and whole.is_contiguous()
+            and all(r._base is whole and tuple(r.shape) == (B, D) and r.is_contiguous()
+                    and r.storage_offset() == whole.storage_offset() + k * B * D for k, r in enumerate(reps))):
+        return q, whole[B:].view(len(cands), B, D)
+    return q, torch.stack(cands, 0)
+
+
+def _require_list_labels(what: str, labels: torch.Tensor, want: tuple, n_cols: int) -> None:
+    if tuple(labels.shape) != want:
+        raise ValueError(f"{what}: with {n_cols} text columns the labels have the shape {want}; "
+                         f"{tuple(labels.shape)} given")
+
+
 class MarginMSELoss(_TupleLoss):
     """mean over the batch of (similarity_fct(query, positive) - similarity_fct(query, negative) - label)^2, the label
     being the teacher's (usually a cross-encoder's) margin score(query, positive) - score(query, negative). With
     `util.pairwise_dot_score` or `util.pairwise_cos_sim` one qst_margin_mse_loss call; any other callable
-    `f(a, b) -> [B]` is called on the embeddings as given and the squared error runs in torch."""
+    `f(a, b) -> [B]` is called on the embeddings as given and the squared error runs in torch.
+    With four or more text columns (query, positive, negatives ...; sentence-transformers 3.x) the labels are [B, K - 1],
+    the teacher's margin against each negative, and the loss is nn.MSELoss() over all of them: one
+    qst_listwise_distill_loss call (csrc/listwise.hip) for the two similarities above and up to 64 candidates, the stacked
+    `similarity_fct` differences in torch otherwise."""
     reduction = "mean"
 
     def __init__(self, model, similarity_fct=util.pairwise_dot_score, fused: bool = True):
@@ -1363,12 +1476,68 @@ class MarginMSELoss(_TupleLoss):
         return None
 
     def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor) -> torch.Tensor:
-        q, p, n = self._embed(sentence_features, 3)
+        cols = list(sentence_features)
+        if len(cols) > 3:
+            return self._forward_list(cols, labels)
+        q, p, n = self._embed(cols, 3)
         sim = self._kernel_sim()
         if sim is not None:
             return margin_mse(q, p, n, labels.view(-1), sim, "mean")
         margin = self.similarity_fct(q, p) - self.similarity_fct(q, n)
         return torch.nn.functional.mse_loss(margin, labels.view(-1).to(margin.dtype))
+
+    def _forward_list(self, cols: List[Dict[str, torch.Tensor]], labels: torch.Tensor) -> torch.Tensor:
+        reps = self._embed(cols, len(cols))
+        K = len(reps) - 1
+        _require_list_labels(type(self).__name__, labels, (reps[0].shape[0], K - 1), len(cols))
+        sim = self._kernel_sim()
+        if sim is not None and K <= LISTWISE_MAX_K:
+            return listwise_distill(*_list_operands(reps), labels, LISTWISE_MARGIN_MSE, sim, 1.0, "mean")
+        pos = self.similarity_fct(reps[0], reps[1])
+        margins = torch.stack([pos - self.similarity_fct(reps[0], n) for n in reps[2:]], dim=1)
+        return torch.nn.functional.mse_loss(margins, labels.to(margins.dtype))
+
+
+class DistillKLDivLoss(_TupleLoss):
+    """sentence-transformers' DistillKLDivLoss (3.4): temperature^2 * KLDivLoss(batchmean) between the teacher's softmax over
+    the K candidates of a query and the student's, both at `temperature`. Two or more text columns (query, positive,
+    negatives ...) and labels [B, K], the teacher's (usually a cross-encoder's) score of every candidate. With
+    `util.pairwise_dot_score` (the default) or `util.pairwise_cos_sim`, recognised by identity, and up to 64 candidates the K
+    similarities, both softmaxes, the divergence and every gradient are one qst_listwise_distill_loss call
+    (csrc/listwise.hip); any other callable `f(a, b) -> [B]` is called once per candidate on the embeddings as given and
+    sentence-transformers' composition runs in torch on the stacked result."""
+    reduction = "mean"
+
+    def __init__(self, model, similarity_fct=util.pairwise_dot_score, temperature: float = 1.0, fused: bool = True):
+        super().__init__(model, fused)
+        self.similarity_fct = similarity_fct
+        self.temperature = temperature
+
+    def get_config_dict(self):
+        return {"similarity_fct": self.similarity_fct.__name__, "temperature": self.temperature}
+
+    def _kernel_sim(self) -> Optional[int]:
+        if self.similarity_fct is util.pairwise_dot_score:
+            return METRIC_DOT
+        if self.similarity_fct is util.pairwise_cos_sim:
+            return METRIC_COS_SIM
+        return None
+
+    def forward(self, sentence_features: Iterable[Dict[str, torch.Tensor]], labels: torch.Tensor) -> torch.Tensor:
+        cols = list(sentence_features)
+        if len(cols) < 2:
+            raise ValueError(f"{type(self).__name__} takes 2 or more text columns per example, {len(cols)} given")
+        reps = self._embed(cols, len(cols))
+        K = len(reps) - 1
+        _require_list_labels(type(self).__name__, labels, (reps[0].shape[0], K), len(cols))
+        sim = self._kernel_sim()
+        if sim is not None and K <= LISTWISE_MAX_K:
+            return listwise_distill(*_list_operands(reps), labels, LISTWISE_KL, sim, self.temperature, "mean")
+        T = self.temperature
+        scores = torch.stack([self.similarity_fct(reps[0], d) for d in reps[1:]], dim=1) / T
+        student = torch.log_softmax(scores, dim=1)
+        teacher = torch.softmax(labels.to(scores.dtype) / T, dim=1)
+        return nn.KLDivLoss(reduction="batchmean")(student, teacher) * (T ** 2)
 
 
 # ------------------------------------------------------------------ pairwise ranking of graded pairs
