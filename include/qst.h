@@ -730,15 +730,17 @@ int qst_rerank_metrics(const float* scores, const int64_t* offsets, const int32_
  * k <= min(nc, 1024). mode: QST_SCORE_DOT (util.dot_score), QST_SCORE_COS (util.cos_sim: both sides normalised first,
  * eps 1e-12) or QST_SCORE_EUCLID (the reference's own euclidean_score, models/evaluators.py:392-405:
  * 1 / (1 + ||q - c||_2), which training/main.py:57 and ir_evauation_script.py:71 pass as 'euclid_score'). Outputs: the
- * k best per query, sorted by descending score (ties: ascending corpus index): out_scores f32 [nq, k], out_index
- * int64 [nq, k]. */
+ * k best per query: out_scores f32 [nq, k], out_index int64 [nq, k], in the order qst_kernels.h states at qst_topk_rows:
+ * a NaN score of either sign first, then descending score with -0.0 = +0.0, then ascending corpus index -- also among
+ * the rows tied at the k-th place. The zero columns that pad the score block are no candidates. */
 enum { QST_SCORE_DOT = 0, QST_SCORE_COS = 1, QST_SCORE_EUCLID = 2 };
 size_t qst_topk_workspace_bytes(int nq, int nc, int dim);
 int qst_topk_scores(const float* queries, const float* corpus, int nq, int nc, int dim, int k, int mode,
                     float* out_scores, int64_t* out_index, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The full score matrix of one of those functions (what util.cos_sim / util.dot_score / euclidean_score return):
- * out f32 [nq, ld_out] with ld_out = nc rounded up to a multiple of 4. */
+ * out f32 [nq, ld_out] with ld_out = nc rounded up to a multiple of 4; columns nc .. ld_out-1 are written with 0.0.
+ * dim % 32 == 0, and any other ld_out is refused (QST_ERR_UNSUPPORTED). */
 size_t qst_score_workspace_bytes(int nq, int nc, int dim);
 int qst_score_matrix(const float* queries, const float* corpus, int nq, int nc, int dim, int mode, float* out,
                      int64_t ld_out, void* workspace, size_t workspace_bytes, void* stream);
@@ -762,7 +764,8 @@ int qst_cls_head_fwd(const float* x, int64_t ldx, int n, int H, const float* w1,
 /* The same with a ceiling: corpus rows scoring above max_score do not take part. This is the reference's negative
  * selection (dataset/quadruplet_dataset.py:185-270: candidates with SBERT cosine <= 0.2 to the reference caption, then
  * hard_contrastive_sampling = the k highest remaining scores, :31-47), for all reference captions at once
- * (SURVEY.md 8f rank 4). Where fewer than k rows qualify the tail of a result row is score -inf, index -1. */
+ * (SURVEY.md 8f rank 4). Where fewer than k rows qualify the tail of a result row is score -inf, index -1. A row with a
+ * NaN score is not above any ceiling and takes part; a NaN max_score is refused (QST_ERR_BAD_ARG) before any launch. */
 int qst_topk_scores_capped(const float* queries, const float* corpus, int nq, int nc, int dim, int k, int mode,
                            float max_score, float* out_scores, int64_t* out_index, void* workspace,
                            size_t workspace_bytes, void* stream);

@@ -386,17 +386,22 @@ int qst_attention_bwd_x3(const float* qkv, const float* ctx, const float* dctx, 
  * the parity-precision training path (element index = flat index, the 16-bit generator of QstDrop). */
 int qst_dropout_apply_f32(const QstDrop* d, const float* in, const float* resid, int64_t n, float* out, void* stream);
 
-/* k best entries of every row of scores f32 [nrows, ld] (first n columns), sorted by descending score (ties: ascending
- * index). index_map (nullable, int64, same ld) translates column numbers into caller ids -- used to merge the
- * per-chunk results of qst_topk_scores. k <= min(n, 1024). */
+/* k best entries of every row of scores f32 [nrows, ld] (first n columns; columns n .. ld-1 are not read). index_map
+ * (nullable, int64, same ld) translates column numbers into caller ids -- used to merge the per-chunk results of
+ * qst_topk_scores; an id is any int64 below INT64_MAX. k <= min(n, 1024).
+ * The order of every top-k of this library (qst_topk_rows, qst_topk_scores(_capped), qst_topk_merge_rows and the
+ * streams): a NaN of either sign and any payload first (above +inf, as torch.topk), then score descending with -0.0
+ * and +0.0 tied, then id ascending (the column without an index_map) -- also among the entries tied at the k-th place,
+ * whatever their number, so the same inputs give the same bits. A NaN comes back as a NaN (payload unspecified), a
+ * zero as +0.0, every other score with the bits it had. */
 int qst_topk_rows(const float* scores, int64_t ld, const int64_t* index_map, int nrows, int n, int k,
                   float* out_scores, int64_t* out_index, void* stream);
 
 /* Streaming top-k: the k best of a row's running result and one more chunk of its scores, so that a corpus of any
  * size goes through in pieces and the answer is the same for every way of cutting it. scores f32 [nrows, ld] (first n
  * columns; column j is global id col_base + j), run_scores f32 / run_index int64 [nrows, k]: the caller fills them with
- * -inf / -1 (= empty) before the first chunk. Order: score descending (NaN above +inf), then id ascending -- also among
- * the entries tied at the k-th place, whatever their number. exclude_self != 0 drops the candidate whose id is
+ * -inf / -1 (= empty) before the first chunk. Order: qst_topk_rows's (NaN first, score descending, id ascending, also among
+ * the entries tied at the k-th place). exclude_self != 0 drops the candidate whose id is
  * row_base + row; candidates above max_score do not take part (+inf: all do). Fewer than k candidates leave the tail
  * -inf / -1. k <= 1024. An id must not reach a row twice (the same chunk merged again). */
 int qst_topk_merge_rows(const float* scores, int64_t ld, int nrows, int n, int64_t col_base, int64_t row_base,

@@ -5,7 +5,9 @@ InformationRetrievalEvaluator computes for the reference (call sites /root/refer
 /root/reference/ir_evauation_script.py:107-131): util.cos_sim / util.dot_score of query vs corpus embeddings
 (float64 here), the top max(k) hits per query, then Accuracy@k, Precision@k, Recall@k, MRR@k, NDCG@k (binary gain,
 log2 discount, ideal = all relevant first), MAP@k (divided by min(k, |relevant|)). Ranking ties break by corpus
-position, which is also what the HIP kernel does. Only tests/ may import this module."""
+position, which is what the HIP kernels do as well, also among the documents tied at the k-th place (csrc/retrieval.hip:
+one integer key for both top-k kernels, the cut decided by id). The scores here are finite; where a NaN can occur the
+yardstick is tests/topk_stream_cases.py (NaN of either sign first). Only tests/ may import this module."""
 import math
 
 import numpy as np

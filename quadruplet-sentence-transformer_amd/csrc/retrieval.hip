@@ -8,10 +8,12 @@
 //
 // Here: rows are normalised (cosine) or copied into a 4-row-padded workspace, the [nq, nc] score matrix comes from the
 // split-bf16 x3 GEMM (fp32-class products: near-ties keep the order an fp32 matmul would give them), and one
-// workgroup per query selects the k best by a 4-pass radix select on order-preserving integer keys, then sorts them.
+// workgroup per query selects the k best by a radix select on integer keys, then sorts them on those keys.
 //
 // qst_topk_stream does the same chunk by chunk for a corpus of any size: each chunk's score block is merged into a
-// running [nq, k] result by topk_merge_kernel, whose ties are decided by global id, so the chunking does not show.
+// running [nq, k] result by topk_merge_kernel. Both kernels share one selection (topk_select_sort_store) and one order:
+// a NaN of either sign first, then score descending with -0.0 = +0.0, then id ascending -- also among the entries tied
+// at the k-th place, so neither wave scheduling nor the chunking shows in a result.
 //
 // qst_community_* (at the end of the file) are sentence-transformers 2.2.2's util.community_detection on the same panels:
 // a count per row, the members of the rows that are asked for, and the greedy claim -- no n x n matrix, no top-k.
@@ -40,99 +42,163 @@ __global__ __launch_bounds__(256) void prep_rows_kernel(const float* x, int n, i
     for (int c = lane; c < dim; c += 64) dst[c] = src[c] * inv;
 }
 
-// order-preserving map float -> uint32 (larger float <=> larger key); NaNs sort above +inf, as torch.topk ranks them
+// The one order of every top-k here, as an integer key (larger key ranks first): every NaN, of either sign and any
+// payload, is the top key 0xFFFFFFFF (above +inf, where torch.topk ranks it); -0.0 and +0.0 share the key of +0.0; the
+// rest is numeric. A negative float is the two's complement of its bits (0x80000000 - magnitude), which puts -0.0 on
+// +0.0's key at no cost; the keys run from 0x00800000 (-inf) to 0xFF800000 (+inf). This sits in the inner loop of every
+// pass of both kernels: a handful of VALU instructions per element, and the time shows each one. No float is compared
+// after this point.
 __device__ __forceinline__ uint32_t fkey(float v) {
     const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    const uint32_t key = (u & 0x80000000u) ? 0u - u : (u | 0x80000000u);
+    return v != v ? 0xFFFFFFFFu : key;
+}
+
+// the score of a key: a NaN (0x7FFFFFFF) for the top key, +0.0 for the zeros' key, otherwise the bits that went in
+__device__ __forceinline__ float fkey_inv(uint32_t key) {
+    return __builtin_bit_cast(float, (key & 0x80000000u) ? (key ^ 0x80000000u) : 0u - key);
 }
 
 constexpr int TOPK_MAX = 1024;
 
-// One workgroup per row. Pass p fixes 8 more bits of the k-th largest key: histogram the digit of every element that
-// still matches the prefix, walk the 256 bins from the top. After 4 passes `prefix` IS the k-th largest key, `need`
-// the number of elements equal to it that belong to the result. Then collect (> prefix: all, == prefix: the first
-// `need` in index order of arrival), sort by (score desc, index asc) with a bitonic network in LDS, write.
-// cap: entries above it do not take part (they rank below everything and come out as -inf / index -1): the
-// "not too similar" filter of negative mining. +inf = plain top-k.
-__global__ __launch_bounds__(256) void topk_rows_kernel(const float* scores, int64_t ld, const int64_t* index_map, int n,
-                                                        int k, float cap, float* out_scores, int64_t* out_index) {
+// What both top-k kernels do once they can enumerate a row's candidates: select the k best by the composite key
+// (fkey(score), id ascending), sort them, store them. `visit(f)` calls f(key, id) for every candidate of this thread
+// and must enumerate the same candidates each time it is called. An id is ranked by its offset from idbase, which is
+// at most id_passes bytes wide; INT64_MAX is not an id (it marks an empty slot).
+//
+// The radix select runs over all of the composite key: four 8-bit passes over the score key, then passes over the id
+// offset's bytes from the top one down, with the digit inverted so that the smaller id is the larger digit. It stops at
+// the first pass whose chosen bin holds exactly what is still needed -- for distinct scores at the cut that is pass 4 at
+// the latest, so the id passes run only when equal scores straddle the cut, and then they decide it by id however many
+// the ties are. The chosen set therefore does not depend on atomic arrival order; the bitonic sort, on the integer keys
+// (descending key, ascending id, empty slots last), orders it. Fewer than k candidates leave a tail of -inf / -1.
+//
+// LDS: 4 KB keys + 8 KB ids + the 1 KB histogram. out_* are written only after the sort.
+template <class Visit>
+__device__ __forceinline__ void topk_select_sort_store(Visit&& visit, uint64_t idbase, int id_passes, int k, float* rs,
+                                                       int64_t* rx) {
     __shared__ uint32_t hist[256];
-    __shared__ uint32_t sh_prefix, sh_need, sh_cnt, sh_cnt_eq;
-    __shared__ float sv[TOPK_MAX];
+    __shared__ uint32_t sh_digit, sh_need, sh_state, sh_cnt;
+    __shared__ uint32_t sk[TOPK_MAX];
     __shared__ int64_t si[TOPK_MAX];
     const int tid = threadIdx.x;
-    const float* row = scores + (size_t)blockIdx.x * ld;
-    const int64_t* imap = index_map ? index_map + (size_t)blockIdx.x * ld : nullptr;
 
-    uint32_t prefix = 0, mask = 0, need = (uint32_t)k;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = 24 - 8 * pass;
+    // after the passes: a candidate is taken iff (key & kmask) > kprefix, or equal with (offset & imask) <= iprefix
+    uint32_t kprefix = 0, kmask = 0, need = (uint32_t)k;
+    uint64_t iprefix = 0, imask = 0;
+    for (int pass = 0; pass < 4 + id_passes; ++pass) {
+        const bool on_key = pass < 4;
+        const int shift = on_key ? 24 - 8 * pass : 8 * (id_passes - 1 - (pass - 4));
         hist[tid] = 0;
         __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            const float v = row[i];
-            const uint32_t key = v > cap ? 0u : fkey(v);
-            if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-        }
+        visit([&](uint32_t key, int64_t id) {
+            const uint64_t off = (uint64_t)id - idbase;
+            if ((key & kmask) != kprefix || (off & imask) != iprefix) return;
+            const uint32_t d = on_key ? (key >> shift) & 255u : 255u - (uint32_t)((off >> shift) & 255u);
+            atomicAdd(&hist[d], 1u);
+        });
         __syncthreads();
         if (tid == 0) {
             uint32_t acc = 0;
             int d = 255;
-            for (; d > 0; --d) {
+            for (; d >= 0; --d) {
                 if (acc + hist[d] >= need) break;
                 acc += hist[d];
             }
-            sh_prefix = prefix | ((uint32_t)d << shift);
-            sh_need = need - acc;                      // still to take among the elements with this digit
+            // d < 0: fewer than `need` candidates in all (only on pass 0): every one is taken
+            sh_state = d < 0 ? 2u : (acc + hist[d] == need ? 1u : 0u);
+            sh_digit = (uint32_t)(d < 0 ? 0 : d);
+            sh_need = need - acc;
         }
         __syncthreads();
-        prefix = sh_prefix;
+        const uint32_t state = sh_state, d = sh_digit;
         need = sh_need;
-        mask |= 255u << shift;
-        __syncthreads();
+        if (state == 2u) break;                            // masks still zero: the rule above takes everything
+        if (on_key) { kprefix |= d << shift; kmask |= 255u << shift; }
+        else { iprefix |= (uint64_t)(255u - d) << shift; imask |= (uint64_t)255u << shift; }
+        if (state == 1u) break;                            // the bin is taken whole: nothing left to decide
     }
-    // collect
-    if (tid == 0) { sh_cnt = 0; sh_cnt_eq = 0; }
-    __syncthreads();
+
     const int kp = k <= 1 ? 1 : 1 << (32 - __builtin_clz((unsigned)(k - 1)));     // next power of two
-    for (int i = tid; i < kp; i += 256) { sv[i] = -INFINITY; si[i] = INT64_MAX; }
+    if (tid == 0) sh_cnt = 0;
+    for (int i = tid; i < kp; i += 256) { sk[i] = 0u; si[i] = INT64_MAX; }
     __syncthreads();
-    for (int i = tid; i < n; i += 256) {
-        const float v0 = row[i];
-        const bool over = v0 > cap;
-        const float v = over ? -INFINITY : v0;
-        const uint32_t key = over ? 0u : fkey(v0);
-        bool take = key > prefix;
-        if (key == prefix) take = atomicAdd(&sh_cnt_eq, 1u) < need;
-        if (take) {
+    visit([&](uint32_t key, int64_t id) {
+        const uint32_t hi = key & kmask;
+        if (hi > kprefix || (hi == kprefix && (((uint64_t)id - idbase) & imask) <= iprefix)) {
             const uint32_t pos = atomicAdd(&sh_cnt, 1u);
-            if (pos < (uint32_t)k) { sv[pos] = v; si[pos] = over ? INT64_MAX : (imap ? imap[i] : (int64_t)i); }
+            if (pos < (uint32_t)k) { sk[pos] = key; si[pos] = id; }     // more than k only if an id came in twice
         }
-    }
+    });
     __syncthreads();
-    // bitonic sort of kp entries: descending score, ascending index among equal scores
+    // bitonic sort of kp entries: descending key, ascending id among equal keys; empty slots (id INT64_MAX) go last
     for (int size = 2; size <= kp; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             for (int t = tid; t < (kp >> 1); t += 256) {
                 const int lo = 2 * t - (t & (stride - 1));
                 const int hi = lo + stride;
                 const bool desc = ((lo & size) == 0);
-                const float a = sv[lo], b = sv[hi];
+                const uint32_t a = sk[lo], b = sk[hi];
                 const int64_t ia = si[lo], ib = si[hi];
-                const bool a_first = (a > b) || (a == b && ia < ib);       // a ranks before b
-                if (desc ? !a_first : a_first) { sv[lo] = b; sv[hi] = a; si[lo] = ib; si[hi] = ia; }
+                const bool ea = ia == INT64_MAX, eb = ib == INT64_MAX;
+                const bool a_first = ea != eb ? eb : (a > b) || (a == b && ia < ib);       // a ranks before b
+                if (desc ? !a_first : a_first) { sk[lo] = b; sk[hi] = a; si[lo] = ib; si[hi] = ia; }
             }
             __syncthreads();
         }
     }
     for (int i = tid; i < k; i += 256) {
-        out_scores[(size_t)blockIdx.x * k + i] = sv[i];
-        out_index[(size_t)blockIdx.x * k + i] = si[i] == INT64_MAX ? -1 : si[i];
+        const bool empty = si[i] == INT64_MAX;
+        rs[i] = empty ? -INFINITY : fkey_inv(sk[i]);
+        rx[i] = empty ? -1 : si[i];
     }
 }
 
-__device__ __forceinline__ float fkey_inv(uint32_t key) {
-    return __builtin_bit_cast(float, (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+// k best of every row of a score matrix: one workgroup per row. The candidates are the row's n scores that are not above
+// cap (the "not too similar" filter of negative mining; +inf = plain top-k; a NaN is not above anything), each with its
+// column or its index_map entry as id. Ids are ranked by their offset from the row's smallest one, so any int64 below
+// INT64_MAX may be an id; without an index_map the span is n - 1 and nothing is scanned for it.
+__global__ __launch_bounds__(256) void topk_rows_kernel(const float* scores, int64_t ld, const int64_t* index_map, int n,
+                                                        int k, float cap, float* out_scores, int64_t* out_index) {
+    __shared__ unsigned long long sh_ext;
+    const int tid = threadIdx.x;
+    const float* row = scores + (size_t)blockIdx.x * ld;
+    const int64_t* imap = index_map ? index_map + (size_t)blockIdx.x * ld : nullptr;
+
+    uint64_t idbase = 0, span = (uint64_t)(n - 1);
+    if (imap) {                                             // (uniform)
+        constexpr uint64_t kBias = 1ull << 63;              // signed order as unsigned order
+        uint64_t lo = ~0ull, hi = 0ull;
+        for (int i = tid; i < n; i += 256) {
+            const uint64_t u = (uint64_t)imap[i] ^ kBias;
+            lo = u < lo ? u : lo;
+            hi = u > hi ? u : hi;
+        }
+        // one LDS word serves both reductions (the minimum as the maximum of the complement): no more LDS than the merge
+        if (tid == 0) sh_ext = 0ull;
+        __syncthreads();
+        if (tid < n) atomicMax(&sh_ext, (unsigned long long)hi);
+        __syncthreads();
+        hi = sh_ext;
+        __syncthreads();
+        if (tid == 0) sh_ext = 0ull;
+        __syncthreads();
+        if (tid < n) atomicMax(&sh_ext, (unsigned long long)~lo);
+        __syncthreads();
+        lo = ~(uint64_t)sh_ext;
+        idbase = lo ^ kBias;
+        span = hi - lo;
+    }
+    const int id_passes = (64 - __builtin_clzll(span | 1ull) + 7) / 8;
+
+    auto visit = [&](auto&& f) {
+        for (int i = tid; i < n; i += 256) {
+            const float v = row[i];
+            if (!(v > cap)) f(fkey(v), imap ? imap[i] : (int64_t)i);
+        }
+    };
+    topk_select_sort_store(visit, idbase, id_passes, k, out_scores + (size_t)blockIdx.x * k,
+                           out_index + (size_t)blockIdx.x * k);
 }
 
 // Merge one chunk's scores into a running top-k: one workgroup per row. The candidates are the n scores of the row (global
@@ -140,23 +206,15 @@ __device__ __forceinline__ float fkey_inv(uint32_t key) {
 // is the row's own (exclude_self) or its score is above cap. The k best by (score descending, id ascending) go back to
 // run_*, real entries first, then -inf / -1.
 //
-// The order is one composite key, (fkey(score), ~id), and the radix select runs over all of it: four 8-bit passes over the
-// score key as in topk_rows_kernel, then passes over the id bytes from the top non-zero byte of the largest id down, with
-// the digit inverted so that the smaller id is the larger digit. It stops at the first pass whose chosen bin holds
-// exactly what is still needed -- for distinct scores at the cut that is pass 4 at the latest, so the id passes run only
-// when equal scores straddle the cut, and then they decide it by id however many the ties are. The chosen set therefore
-// does not depend on atomic arrival order or on how the columns were cut into chunks; the bitonic sort orders it.
+// Selection and sort are topk_select_sort_store's, over ids counted from 0 (the id passes start at the top non-zero byte
+// of the largest id): the chosen set does not depend on atomic arrival order or on how the columns were cut into chunks.
 //
 // The old running row lives in registers (k <= 1024 = 4 per thread) from before the first barrier; run_* is written only
-// after the sort. LDS: 4 KB keys + 8 KB ids + the 1 KB histogram.
+// after the sort.
 __global__ __launch_bounds__(256) void topk_merge_kernel(const float* scores, int64_t ld, int n, int64_t col_base,
                                                          int64_t row_base, int exclude_self, float cap, int k,
                                                          float* run_scores, int64_t* run_index) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t sh_digit, sh_need, sh_state, sh_cnt;
     __shared__ unsigned long long sh_idmax;
-    __shared__ uint32_t sk[TOPK_MAX];
-    __shared__ int64_t si[TOPK_MAX];
     const int tid = threadIdx.x;
     const float* row = scores + (size_t)blockIdx.x * ld;
     float* rs = run_scores + (size_t)blockIdx.x * k;
@@ -190,75 +248,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* scores, in
         for (int e = 0; e < 4; ++e)
             if (ri[e] >= 0 && ri[e] != self && !(rv[e] > cap)) f(fkey(rv[e]), ri[e]);
     };
-
-    // after the passes: a candidate is taken iff (key & kmask) > kprefix, or equal with (id & imask) <= iprefix
-    uint32_t kprefix = 0, kmask = 0, need = (uint32_t)k;
-    uint64_t iprefix = 0, imask = 0;
-    for (int pass = 0; pass < 4 + id_passes; ++pass) {
-        const bool on_key = pass < 4;
-        const int shift = on_key ? 24 - 8 * pass : 8 * (id_passes - 1 - (pass - 4));
-        hist[tid] = 0;
-        __syncthreads();
-        visit([&](uint32_t key, int64_t id) {
-            if ((key & kmask) != kprefix || ((uint64_t)id & imask) != iprefix) return;
-            const uint32_t d = on_key ? (key >> shift) & 255u : 255u - (uint32_t)(((uint64_t)id >> shift) & 255u);
-            atomicAdd(&hist[d], 1u);
-        });
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t acc = 0;
-            int d = 255;
-            for (; d >= 0; --d) {
-                if (acc + hist[d] >= need) break;
-                acc += hist[d];
-            }
-            // d < 0: fewer than `need` candidates in all (only on pass 0): every one is taken
-            sh_state = d < 0 ? 2u : (acc + hist[d] == need ? 1u : 0u);
-            sh_digit = (uint32_t)(d < 0 ? 0 : d);
-            sh_need = need - acc;
-        }
-        __syncthreads();
-        const uint32_t state = sh_state, d = sh_digit;
-        need = sh_need;
-        if (state == 2u) break;                            // masks still zero: the rule above takes everything
-        if (on_key) { kprefix |= d << shift; kmask |= 255u << shift; }
-        else { iprefix |= (uint64_t)(255u - d) << shift; imask |= (uint64_t)255u << shift; }
-        if (state == 1u) break;                            // the bin is taken whole: nothing left to decide
-    }
-
-    const int kp = k <= 1 ? 1 : 1 << (32 - __builtin_clz((unsigned)(k - 1)));     // next power of two
-    if (tid == 0) sh_cnt = 0;
-    for (int i = tid; i < kp; i += 256) { sk[i] = 0u; si[i] = INT64_MAX; }
-    __syncthreads();
-    visit([&](uint32_t key, int64_t id) {
-        const uint32_t hi = key & kmask;
-        if (hi > kprefix || (hi == kprefix && ((uint64_t)id & imask) <= iprefix)) {
-            const uint32_t pos = atomicAdd(&sh_cnt, 1u);
-            if (pos < (uint32_t)k) { sk[pos] = key; si[pos] = id; }     // more than k only if an id came in twice
-        }
-    });
-    __syncthreads();
-    // bitonic sort of kp entries: descending key, ascending id among equal keys; empty slots (id INT64_MAX) go last
-    for (int size = 2; size <= kp; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (kp >> 1); t += 256) {
-                const int lo = 2 * t - (t & (stride - 1));
-                const int hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const uint32_t a = sk[lo], b = sk[hi];
-                const int64_t ia = si[lo], ib = si[hi];
-                const bool ea = ia == INT64_MAX, eb = ib == INT64_MAX;
-                const bool a_first = ea != eb ? eb : (a > b) || (a == b && ia < ib);       // a ranks before b
-                if (desc ? !a_first : a_first) { sk[lo] = b; sk[hi] = a; si[lo] = ib; si[hi] = ia; }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < k; i += 256) {
-        const bool empty = si[i] == INT64_MAX;
-        rs[i] = empty ? -INFINITY : fkey_inv(sk[i]);
-        rx[i] = empty ? -1 : si[i];
-    }
+    topk_select_sort_store(visit, 0ull, id_passes, k, rs, rx);
 }
 
 // Euclidean score 1 / (1 + ||q - c||_2): the reference's own third score function (models/evaluators.py:392-405,

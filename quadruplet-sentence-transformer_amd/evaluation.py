@@ -269,7 +269,9 @@ class InformationRetrievalEvaluator(SentenceEvaluator):
     ir_evauation_script.py:71). Entries that are, or behave like, cosine / dot / 1/(1+L2) scoring run as ONE fused
     libqst call per corpus chunk (qst_topk_scores); any other callable is called and its matrix goes through
     qst_topk_rows (see resolve_score_function). Per-chunk results are merged by a second top-k over the candidates;
-    only the metric arithmetic is host Python."""
+    only the metric arithmetic is host Python. Equal scores (duplicate documents) rank by corpus position, also at the
+    max(k) cut and across chunks, and a NaN score of either sign ranks first: the hit lists do not depend on
+    corpus_chunk_size."""
 
     def __init__(self, queries: Dict[str, str], corpus: Dict[str, str], relevant_docs: Dict[str, Set[str]],
                  corpus_chunk_size: int = 50000, mrr_at_k: List[int] = [10], ndcg_at_k: List[int] = [10],
@@ -380,7 +382,8 @@ class InformationRetrievalEvaluator(SentenceEvaluator):
         out = {}
         for nm in self.score_function_names:
             sc, idx = best[nm][0].cpu().numpy(), best[nm][1].cpu().numpy()
-            results = [[{"corpus_id": self.corpus_ids[int(c)], "score": float(s)} for s, c in zip(sc[qi], idx[qi])]
+            # an id < 0 is an empty slot of the top-k (fewer candidates than k): it is no document
+            results = [[{"corpus_id": self.corpus_ids[int(c)], "score": float(s)} for s, c in zip(sc[qi], idx[qi]) if c >= 0]
                        for qi in range(len(self.queries_ids))]
             out[nm] = ir_metrics(results, self.queries_ids, self.relevant_docs, self.mrr_at_k, self.ndcg_at_k,
                                  self.accuracy_at_k, self.precision_recall_at_k, self.map_at_k)

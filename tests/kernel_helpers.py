@@ -4,16 +4,20 @@
     types (OPDT, opr, kf) and the ctypes argument structs filled from keywords (gemm_args, ln_epi, ffn_args, attn_desc);
   * references and layouts more than one file compares against: attn_ref (re-exported from attention_mask_cases, which the
     host test imports without the library), the dropout state / descriptor, the MX scale layout (stage_major, row_major) and
-    the MXFP8 quantisation of an operand on the device (quant_dev);
+    the MXFP8 quantisation of an operand on the device (quant_dev), the real-valued top-k cases with their fp64 yardstick (real_rows, real_case) and the
+    streaming top-k call both top-k files compare with (new_topk_state, topk_stream_call);
   * the encoder harness: quad_batch and run_step, one training forward + quadruplet loss + backward of a fresh HipEncoder.
 
 The rule: a helper lives in the test file that uses it; its second user moves it here instead of copying it. What a test
 asserts stays in its own file. tests/test_kernel_coverage_host.py reads the test files, not this module: an entry point is
 called by name (`lib.NAME`, `kf(lib, "NAME", op)`) from a test, never only from here.
 """
+import functools
+
 import pytest
 import torch
 
+import topk_stream_cases as T
 from attention_mask_cases import attn_ref  # noqa: F401  (moved there with its second user, the host test: re-exported)
 from oracle import dropout_ref as D
 from quadruplet_sentence_transformer_amd import _lib
@@ -116,6 +120,42 @@ def quant_dev(lib, x, bf16=False):
     s = torch.zeros((K + 127) // 128 * rows * 4, dtype=torch.uint8, device="cuda")
     _lib.check(lib.qst_quant_mx(src.data_ptr(), int(bf16), rows, K, q.data_ptr(), s.data_ptr(), stream()))
     return q, s
+
+
+def real_rows(nq, nc, dim, seed):
+    """Gaussian query and corpus rows (host fp32) of a real-valued top-k case: topk_stream_cases.REAL_CASES / REAL_SEED."""
+    g = torch.Generator().manual_seed(seed + dim)
+    return torch.randn(nq, dim, generator=g), torch.randn(nc, dim, generator=g)
+
+
+@functools.lru_cache(maxsize=None)
+def real_case(nq, nc, k, chunk, dim, mode):
+    """One of topk_stream_cases.REAL_CASES with its fp64 yardstick, computed once for every test that judges against it (and
+    left unchanged by all of them): (q, c, fp64 score matrix, fp64 top-k values, fp64 top-k ids)."""
+    q, c = real_rows(nq, nc, dim, T.REAL_SEED[(nq, nc, k, chunk)])
+    full = T.scores_ref(q.numpy(), c.numpy(), mode)
+    want_s, want_i = T.topk_ref(full, k)
+    return q, c, full, want_s, want_i
+
+
+def new_topk_state(rows, k):
+    """An empty running top-k: scores -inf, ids -1."""
+    return (torch.full((rows, k), -float("inf"), dtype=torch.float32, device="cuda"),
+            torch.full((rows, k), -1, dtype=torch.int64, device="cuda"))
+
+
+def topk_stream_call(lib, q, c, k, mode, chunk, query_base=0, corpus_base=0, exclude_self=0, max_score=float("inf"),
+                     state=None):
+    """qst_topk_stream on q, c (device fp32 [nq, dim], [nc, dim]) with a workspace of exactly the size it asks for; returns
+    the running (scores, ids). The streaming tests call the entry point by name themselves as well."""
+    nq, dim = q.shape
+    nc = c.shape[0]
+    rs, ri = new_topk_state(nq, k) if state is None else state
+    ws = torch.empty(lib.qst_topk_stream_workspace_bytes(nq, min(chunk, nc), dim), dtype=torch.uint8, device="cuda")
+    rc = lib.qst_topk_stream(q.data_ptr(), c.data_ptr(), nq, nc, dim, k, mode, chunk, query_base, corpus_base, exclude_self,
+                             max_score, rs.data_ptr(), ri.data_ptr(), ws.data_ptr(), ws.numel(), stream())
+    assert rc == 0
+    return rs, ri
 
 
 # ------------------------------------------------------------------ encoder harness

@@ -1,6 +1,9 @@
 """GPU: retrieval scoring + top-k kernels (libqst qst_topk_rows / qst_topk_scores) against the fp64 oracle, and the
 InformationRetrievalEvaluator end to end (encode -> score -> top-k across corpus chunks -> metrics) against the same
-metrics computed by the oracle from the model's own embeddings."""
+metrics computed by the oracle from the model's own embeddings. The last section holds the Python
+surface to the order the kernels promise (tests/test_gpu_topk_oneshot.py checks the entry points themselves): duplicate
+documents rank by corpus position for every chunking, a host-style NaN of a foreign score function ranks first and no empty
+slot is looked up as a document, duplicated mining candidates come back in id order."""
 import os
 
 import numpy as np
@@ -10,7 +13,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import quadruplet_sentence_transformer_amd  # noqa: E402,F401
-from quadruplet_sentence_transformer_amd import _lib, util  # noqa: E402
+import topk_stream_cases as T  # noqa: E402
+from quadruplet_sentence_transformer_amd import _lib, evaluation, util  # noqa: E402
 from quadruplet_sentence_transformer_amd.evaluation import InformationRetrievalEvaluator  # noqa: E402
 from quadruplet_sentence_transformer_amd.sentence_transformer import SentenceTransformer  # noqa: E402
 from oracle import ir_oracle  # noqa: E402
@@ -36,11 +40,14 @@ def test_topk_rows_matches_a_full_sort(rows, n, k):
         assert len(set(got_idx[r].tolist())) == k                                 # no element taken twice
         strictly = want[r] > want[r][-1]                                          # above the cut: the choice is forced
         np.testing.assert_array_equal(got_idx[r][strictly], order[r][strictly])
+    np.testing.assert_array_equal(got_idx, order)             # ... and AT the cut it is the smaller index: the full sort
     # index_map translates columns into caller ids
     imap = torch.arange(n, dtype=torch.int64).flip(0).repeat(rows, 1).cuda() + 1000
     vals2, idx2 = util.topk_rows(sd, k, index_map=imap)
     np.testing.assert_array_equal(vals2.cpu().numpy(), want)
     np.testing.assert_array_equal(np.take_along_axis(s.numpy(), (n - 1) - (idx2.cpu().numpy() - 1000), axis=1), want)
+    # the ids are the columns reversed: among equal scores the smaller ID is the LARGER column, also at the cut
+    np.testing.assert_array_equal(idx2.cpu().numpy(), T.topk_ref(s.numpy(), k, ids=imap.cpu().numpy())[1])
 
 
 def test_topk_rows_bad_arguments():
@@ -253,3 +260,206 @@ def test_hard_negative_mining_matches_brute_force():
     assert torch.equal(i3, i4) and torch.allclose(s3, s4)
     with pytest.raises(ValueError):
         util.mine_hard_negatives(refs, cands, 4)
+
+
+# ------------------------------------------------------------------ exact ties and NaNs through the Python surface
+class _NoNegativeIndex(list):
+    """corpus_ids that refuses what list[-1] would silently answer with the LAST document."""
+
+    def __getitem__(self, i):
+        assert i >= 0, f"corpus_ids[{i}]: an empty top-k slot was looked up as a document"
+        return list.__getitem__(self, i)
+
+
+def _fp64_dot(a, b):
+    """A foreign callable: a @ b.T accumulated in fp64 and rounded once, so that the score of a duplicated document has the
+    same bits wherever its column lies and however the corpus is chunked (an fp32 matmul may pick another kernel per shape)."""
+    return (a.double() @ b.double().T).float()
+
+
+def _duplicate_corpus(model, max_k=10):
+    """90 documents and 23 queries on `model`, with duplicate documents planted from the fp64 ranking of the model's own
+    embeddings: for some queries the document at the LAST place of the top max_k gets a copy at least 40 positions away
+    (another chunk at chunk sizes 17 and 40), before or after it in turn, so that the two tie exactly across the cut; for
+    others (in turn) the document at the third place, so that both copies are inside. A copy repeats the text and, so that it is
+    bit-identical whatever batch it was encoded in, the embedding row. Of a pair only the copy with the LARGER position is
+    relevant: the wrong choice at the cut changes every metric. Returns queries, corpus, relevant, corpus embeddings
+    (device), query embeddings (numpy), the pairs."""
+    corpus = {f"d{i}": _HashTexts.make(i, 5 + i % 9) for i in range(90)}
+    rng = np.random.RandomState(7)
+    queries, bases = {}, []
+    for qn in range(23):
+        base = rng.randint(0, 90)
+        queries[f"q{qn}"] = corpus[f"d{base}"] + " " + _HashTexts.make(1000 + qn, 2)
+        bases.append(base)
+    q_emb = model.encode(list(queries.values()), batch_size=16, convert_to_numpy=True)
+    c = model.encode(list(corpus.values()), batch_size=16, convert_to_numpy=True).copy()
+    used, pairs, relevant = set(), [], {f"q{qn}": {f"d{bases[qn]}"} for qn in range(23)}
+    for t, qn in enumerate(range(0, 23, 2)):
+        s = ir_oracle.scores(q_emb[qn:qn + 1], c, "dot")[0]
+        order = np.lexsort((np.arange(90), -s))
+        j1 = int(order[max_k - 1] if t % 2 == 0 else order[2])
+        far = [j for j in range(90) if abs(j - j1) >= 40 and j not in used and j not in bases
+               and j not in order[:max_k + 2].tolist()]
+        far = [j for j in far if (j < j1) == (t % 4 < 2)] or far
+        if j1 in used or not far:
+            continue
+        j2 = far[len(far) // 2]
+        c[j2] = c[j1]
+        corpus[f"d{j2}"] = corpus[f"d{j1}"]
+        used |= {j1, j2}
+        pairs.append((qn, j1, j2))
+        relevant[f"q{qn}"].add(f"d{max(j1, j2)}")
+    return queries, corpus, relevant, torch.from_numpy(c).cuda(), q_emb, pairs
+
+
+def _hits_per_function(monkeypatch, ev, model, c_dev):
+    """compute_metrices with the hit lists it hands to ir_metrics recorded: ({name: metrics}, {name: hit lists})."""
+    seen, real = [], evaluation.ir_metrics
+    monkeypatch.setattr(evaluation, "ir_metrics", lambda results, *a, **kw: (seen.append(results), real(results, *a, **kw))[1])
+    got = ev.compute_metrices(model, corpus_embeddings=c_dev)
+    monkeypatch.setattr(evaluation, "ir_metrics", real)
+    assert len(seen) == len(ev.score_function_names)
+    return got, dict(zip(ev.score_function_names, seen))
+
+
+def _hit_arrays(ev, hits, k):
+    pos = {cid: j for j, cid in enumerate(ev.corpus_ids)}
+    s = np.full((len(hits), k), -np.inf, dtype=np.float64)
+    i = np.full((len(hits), k), -1, dtype=np.int64)
+    for r, row in enumerate(hits):
+        s[r, :len(row)] = [h["score"] for h in row]
+        i[r, :len(row)] = [pos[h["corpus_id"]] for h in row]
+    return s, i
+
+
+def test_ir_evaluator_duplicate_documents_rank_by_corpus_position_for_every_chunking(monkeypatch):
+    model = SentenceTransformer("tiny-bert", device="cuda")
+    queries, corpus, relevant, c_dev, q_emb, pairs = _duplicate_corpus(model)
+    c64 = c_dev.cpu().numpy()
+    ks = dict(mrr_at_k=[10], ndcg_at_k=[10], accuracy_at_k=[1, 3, 5, 10], precision_recall_at_k=[1, 3, 5, 10], map_at_k=[10])
+    fns = {"cos_sim": util.cos_sim, "dot_score": util.dot_score, "foreign": _fp64_dot}
+    mode = {"cos_sim": "cos", "dot_score": "dot", "foreign": "dot"}
+    # the yardstick first: exact ties across the cut and inside the list do occur (fp64 scores of identical rows are equal)
+    full = {nm: ir_oracle.scores(q_emb, c64, mode[nm]) for nm in fns}
+    want = {nm: T.topk_ref(full[nm], 11) for nm in fns}
+    across = sum(1 for r in range(23) if want["dot_score"][0][r, 9] == want["dot_score"][0][r, 10])
+    inside = sum(1 for r in range(23) if (np.diff(want["dot_score"][0][r, :10]) == 0).any())
+    assert len(pairs) >= 6 and across >= 3 and inside >= 2, (pairs, across, inside)
+    runs = {}
+    for chunk in (17, 40, len(corpus)):
+        ev = InformationRetrievalEvaluator(queries, corpus, relevant, corpus_chunk_size=chunk, batch_size=16, score_functions=fns,
+                                           **ks)
+        ev._resolved = {"cos_sim": ("native", 1), "dot_score": ("native", 0), "foreign": ("callable", _fp64_dot)}
+        ev.corpus_ids = _NoNegativeIndex(ev.corpus_ids)
+        runs[chunk] = _hits_per_function(monkeypatch, ev, model, c_dev)
+    got, hits = runs[len(corpus)]
+    for chunk in (17, 40):
+        assert runs[chunk][1] == hits, chunk                  # the same hit lists, ids and score bits, for every chunking
+        assert runs[chunk][0] == got, chunk                   # ... and so every metric
+    for nm in fns:
+        assert all(len(h) == 10 for h in hits[nm])
+        gs, gi = _hit_arrays(ev, hits[nm], 10)
+        wi = want[nm][1][:, :10]
+        scale = float(np.abs(full[nm]).max())
+        n_bad = T.ranking_disagreements(gs, gi, full[nm], wi, lambda s: 2e-5 * scale)
+        assert n_bad <= 2
+        for r, p in zip(*np.where(gi != wi)):                 # two ids may trade places only where fp32 cannot tell them apart
+            assert full[nm][r, gi[r, p]] != full[nm][r, wi[r, p]], (nm, r, p)      # ... never where they tie exactly
+        ranked = [[h["corpus_id"] for h in row] for row in hits[nm]]
+        mw = ir_oracle.metrics(ranked, [relevant[q] for q in ev.queries_ids], ks["mrr_at_k"], ks["ndcg_at_k"],
+                               ks["accuracy_at_k"], ks["precision_recall_at_k"], ks["map_at_k"])
+        for metric in mw:
+            for k in mw[metric]:
+                assert got[nm][metric][k] == pytest.approx(mw[metric][k], abs=1e-9), (nm, metric, k)
+    for qn, j1, j2 in pairs:                                  # said directly for the planted pairs, on the exact callable
+        ids = [int(x) for x in _hit_arrays(ev, hits["foreign"], 10)[1][qn]]
+        if max(j1, j2) in ids:
+            assert ids.index(min(j1, j2)) + 1 == ids.index(max(j1, j2)), (qn, j1, j2, ids)
+
+
+def test_ir_evaluator_host_style_nans_of_a_foreign_callable(monkeypatch):
+    """A NaN with the sign bit set (0xFFC00000: what inf - inf and 0 / 0 give on the host) in a few cells of a foreign score
+    matrix: those documents rank first, by corpus position, nothing else is displaced and no id -1 is looked up."""
+    model = SentenceTransformer("tiny-bert", device="cuda")
+    queries, corpus, relevant, c_dev, q_emb, pairs = _duplicate_corpus(model)
+    _, j1, j2 = pairs[0]
+    lone = next(j for j in range(90) if all(j not in p[1:] for p in pairs))
+    poison = [(c_dev[j1].clone(), [0, 1, 2]), (c_dev[lone].clone(), [1, 5])]          # a duplicated document and a single one
+
+    def nan_fn(a, b):
+        out = _fp64_dot(a, b)
+        bits = out.view(torch.int32)
+        for row, qrows in poison:
+            for col in (b == row).all(1).nonzero().flatten().tolist():
+                bits[qrows, col] = -4194304                                           # 0xFFC00000
+        return out
+
+    q_dev = torch.from_numpy(q_emb).cuda()
+    whole = nan_fn(q_dev, c_dev).cpu().numpy()
+    assert whole.view(np.uint32)[1, lone] == 0xFFC00000 and np.isnan(whole[0, [j1, j2]]).all()
+    want_s, want_i = T.topk_ref(whole, 10)
+    np.testing.assert_array_equal(want_i[1, :3], sorted([j1, j2, lone]))
+    ks = dict(mrr_at_k=[10], ndcg_at_k=[10], accuracy_at_k=[1, 10], precision_recall_at_k=[1, 10], map_at_k=[10])
+    for chunk in (17, 40, 90):
+        ev = InformationRetrievalEvaluator(queries, corpus, relevant, corpus_chunk_size=chunk, batch_size=16,
+                                           score_functions={"foreign": nan_fn}, **ks)
+        ev._resolved = {"foreign": ("callable", nan_fn)}
+        ev.corpus_ids = _NoNegativeIndex(ev.corpus_ids)
+        _, hits = _hits_per_function(monkeypatch, ev, model, c_dev)
+        gs, gi = _hit_arrays(ev, hits["foreign"], 10)
+        np.testing.assert_array_equal(gi, want_i)                                     # every id the yardstick's, in its order
+        np.testing.assert_array_equal(gs, want_s.astype(np.float64))
+        assert (gi >= 0).all()
+
+
+def test_hard_negative_mining_duplicated_candidates_come_back_in_id_order():
+    g = torch.Generator().manual_seed(17)
+    R_, C_, D, k = 12, 700, 128, 6
+    q = torch.randn(R_, D, generator=g)
+    qn, c = q.numpy(), torch.randn(C_, D, generator=g).numpy()
+    # a threshold no score comes near: the widest gap between two fp64 scores in (0, 0.1), so that fp32 scores (within 2e-5)
+    # qualify exactly when the fp64 ones do. Copying a candidate row adds no new score value to any reference's row.
+    v = np.sort(ir_oracle.scores(qn, c, "cos").ravel())
+    v = v[(v > 0.0) & (v < 0.1)]
+    at = int(np.argmax(np.diff(v)))
+    thr = float(0.5 * (v[at] + v[at + 1]))
+    assert v[at + 1] - v[at] > 1e-4
+    used, across, inside = set(), [], []
+    for r in range(R_):                                   # from the fp64 ranking: a copy of the row's last (or second) choice
+        s = ir_oracle.scores(qn[r:r + 1], c, "cos")[0]
+        order = [int(j) for j in np.lexsort((np.arange(C_), -s)) if s[j] <= thr]
+        j1 = order[k - 1] if r % 2 == 0 else order[1]
+        far = [j for j in range(C_) if abs(j - j1) > 256 and j not in used and j not in order[:k + 2]]
+        far = [j for j in far if (j < j1) == (r % 4 < 2)] or far
+        if j1 in used:
+            continue
+        j2 = far[len(far) // 3]                           # more than 256 columns away: another trip of the row loop
+        c[j2] = c[j1]
+        used |= {j1, j2}
+        (across if r % 2 == 0 else inside).append((r, min(j1, j2), max(j1, j2)))
+    full = ir_oracle.scores(qn, c, "cos")
+    want_s, want_i = T.topk_ref(full, k + 1, max_score=thr)
+    across = [(r, a, b) for r, a, b in across if want_i[r, k - 1] == a and want_i[r, k] == b]     # still tied across the cut
+    inside = [(r, a, b) for r, a, b in inside if a in want_i[r, :k] and b in want_i[r, :k]]
+    assert len(across) >= 3 and len(inside) >= 3
+    idx, sc = util.mine_hard_negatives(q.cuda(), torch.from_numpy(c).cuda(), k, threshold=thr)
+    gi, gs = idx.cpu().numpy(), sc.cpu().numpy()
+    assert T.ranking_disagreements(gs, gi, full, want_i[:, :k], lambda s: 2e-5) <= 2
+    for r, a, b in across:
+        assert gi[r, k - 1] == a and b not in gi[r]       # of the two tied at the last place, the smaller id
+    for r, a, b in inside:
+        pa = gi[r].tolist().index(a)
+        assert gi[r, pa + 1] == b and gs[r, pa].tobytes() == gs[r, pa + 1].tobytes()
+    # fewer qualifying candidates than k: the duplicates in id order, then the documented tail (-1, -inf)
+    small = c[:8].copy()
+    s = ir_oracle.scores(qn[:1], small, "cos")[0]
+    by = np.argsort(s)
+    small[by[7]] = small[by[1]]                           # the second-lowest candidate copied over the highest
+    s = ir_oracle.scores(qn[:1], small, "cos")[0]
+    u = np.unique(s)
+    assert len(u) == 7 and u[2] - u[1] > 1e-3 and s[by[1]] == s[by[7]] == u[1]
+    thr2 = float(0.5 * (u[1] + u[2]))                     # three qualify: the lowest and the two copies
+    idx2, sc2 = util.mine_hard_negatives(q[:1].cuda(), torch.from_numpy(small).cuda(), 6, threshold=thr2)
+    np.testing.assert_array_equal(idx2.cpu().numpy()[0], [min(by[1], by[7]), max(by[1], by[7]), by[0], -1, -1, -1])
+    assert (sc2[0, 3:] == -float("inf")).all() and sc2[0, 0] == sc2[0, 1] and (sc2[0, :3] <= thr2).all()

@@ -13,17 +13,13 @@ pytestmark = pytest.mark.gpu
 
 import quadruplet_sentence_transformer_amd  # noqa: E402,F401
 import topk_stream_cases as T  # noqa: E402
-from kernel_helpers import lib, stream  # noqa: E402,F401
+from kernel_helpers import lib, new_topk_state, real_case, real_rows, stream, topk_stream_call  # noqa: E402,F401
 from quadruplet_sentence_transformer_amd import _lib, util  # noqa: E402
 from quadruplet_sentence_transformer_amd.evaluation import ParaphraseMiningEvaluator, paraphrase_metrics  # noqa: E402
 from quadruplet_sentence_transformer_amd.sentence_transformer import SentenceTransformer  # noqa: E402
 
 INF = float("inf")
-
-
-def new_state(rows, k):
-    return (torch.full((rows, k), -INF, dtype=torch.float32, device="cuda"),
-            torch.full((rows, k), -1, dtype=torch.int64, device="cuda"))
+new_state = new_topk_state
 
 
 def merge(lib, s, k, cuts, col_base=0, row_base=0, exclude_self=0, max_score=INF, state=None):
@@ -142,22 +138,8 @@ def test_merge_rows_bad_arguments(lib):
 
 
 # ------------------------------------------------------------------ 2. qst_topk_stream, exact
-def stream_call(lib, q, c, k, mode, chunk, query_base=0, corpus_base=0, exclude_self=0, max_score=INF, state=None):
-    """q, c: device fp32 [nq, dim], [nc, dim]."""
-    nq, dim = q.shape
-    nc = c.shape[0]
-    rs, ri = new_state(nq, k) if state is None else state
-    ws = torch.empty(lib.qst_topk_stream_workspace_bytes(nq, min(chunk, nc), dim), dtype=torch.uint8, device="cuda")
-    rc = lib.qst_topk_stream(q.data_ptr(), c.data_ptr(), nq, nc, dim, k, mode, chunk, query_base, corpus_base, exclude_self,
-                             max_score, rs.data_ptr(), ri.data_ptr(), ws.data_ptr(), ws.numel(), stream())
-    assert rc == 0
-    return rs, ri
-
-
-def exact_scores(q, c, dim):
-    full = T.scores_ref(q, c, "dot")
-    assert np.array_equal(full, np.rint(full)) and np.abs(full).max() <= dim     # integers the x3 products hold exactly
-    return full.astype(np.float32)
+stream_call = topk_stream_call          # q, c: device fp32 [nq, dim], [nc, dim]
+exact_scores = T.exact_scores
 
 
 @pytest.mark.parametrize("dim", [32, 64])
@@ -224,34 +206,19 @@ def test_stream_bad_arguments(lib):
 
 
 # ------------------------------------------------------------------ 3. qst_topk_stream, real-valued
-# Seeds: with an fp32 matmul (cos, dot) or fp32 differences (euclid) standing in for the device, each of these cases stays
-# inside its cap of ranking disagreements with the fp64 order (checked on the CPU when the seeds were chosen: the two
-# small-k cases had none against a cap of 2; the k = 1024 case, which ranks all 515 rows, had 2 to 10 against a cap of 665,
-# and 74 for euclid at dim 384).
-REAL_CASES = [(33, 1000, 10, 256), (4, 3000, 100, 1024), (130, 515, 1024, 200)]
-REAL_SEED = {(33, 1000, 10, 256): 101, (4, 3000, 100, 1024): 102, (130, 515, 1024, 200): 103}
-
-
-def real_rows(nq, nc, dim, seed):
-    g = torch.Generator().manual_seed(seed + dim)
-    return torch.randn(nq, dim, generator=g), torch.randn(nc, dim, generator=g)
+# The cases, their seeds (and how they were chosen), the tolerances and the cap: topk_stream_cases, shared with the one-shot
+# tests; the rows themselves: kernel_helpers.real_rows.
+REAL_CASES, REAL_SEED = T.REAL_CASES, T.REAL_SEED
 
 
 @pytest.mark.parametrize("mode", ["cos", "dot", "euclid"])
 @pytest.mark.parametrize("dim", [64, 384])
 @pytest.mark.parametrize("nq,nc,k,chunk", REAL_CASES)
 def test_stream_matches_the_fp64_ranking(lib, nq, nc, k, chunk, dim, mode):
-    q, c = real_rows(nq, nc, dim, REAL_SEED[(nq, nc, k, chunk)])
-    full = T.scores_ref(q.numpy(), c.numpy(), mode)
-    want_s, want_i = T.topk_ref(full, k)
+    q, c, full, want_s, want_i = real_case(nq, nc, k, chunk, dim, mode)
     rs, ri = stream_call(lib, q.cuda(), c.cuda(), k, {"dot": 0, "cos": 1, "euclid": 2}[mode], chunk)
-    if mode == "euclid":
-        tol = lambda s: 2e-6 * abs(s) + 1e-7                                        # fp32 FMA chain + sqrt + rcp
-    else:
-        atol = 2e-5 * float(np.abs(want_s[np.isfinite(want_s)]).max())              # split-bf16 x3 products
-        tol = lambda s: atol
-    n_bad = T.ranking_disagreements(rs.cpu().numpy(), ri.cpu().numpy(), full, want_i, tol)
-    assert n_bad <= max(2, nq * k // 200)
+    n_bad = T.ranking_disagreements(rs.cpu().numpy(), ri.cpu().numpy(), full, want_i, T.real_tol(mode, want_s))
+    assert n_bad <= T.real_cap(nq, k)
 
 
 # ------------------------------------------------------------------ 4. the Python surface
